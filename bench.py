@@ -1,20 +1,31 @@
 #!/usr/bin/env python
 """bench.py -- episodes/sec of the CAPE episodic TRAINING step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one pass of the hot path over one batch of synthetic episodes: forward (backbone, encoder,
 support encoder, decoder), fused criterion, backward, gradient all-reduce (N > 1), global-norm clip,
 AdamW -- dropout ON (train mode); fp32 storage and accumulation, the GEMMs as a bf16x3 split on the bf16 matrix cores by
-default (CAPE_GEMM_PRECISION=f32 = exact fp32 MFMA; that leg is timed too and reported as `alt_exact_f32`).
+default (CAPE_GEMM_PRECISION=f32 = exact fp32 MFMA).
 Workload = BASELINE.json configs[1]:
 1-shot, 256x256, 17 keypoints, ResNet-50 + deformable transformer, 16 episodes x 2 queries per GPU.
 Weak scaling: every rank processes its own 16 episodes (pure data parallel, episodes are independent).
-Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.  At N = 1 the line also carries
-`decode` (BASELINE configs[4]: 5-shot KV-cached autoregressive decode at 512x512 with 68 support keypoints -- time per decode
-step, tokens/s, eager and replayed hipGraphs, against the weight-streaming roof) and `pck_check` (the same synthetic
-episode decoded by the product and by the CPU oracle: PCK@0.2 of both, token streams compared).
+Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+The optimizer runs at learning rate 0: the AdamW kernel does all of its work (moments, clip, weight re-pack) but leaves the
+weights as they are, so every step computes from the same seeded weights.  Its backward reductions are float atomics, and
+this model turns their arrival-order rounding into ~3e-3 of the gradient (profiles/r02_determinism.txt); a real learning rate
+would feed that back into the next step's forward pass and no two runs would compute the same losses.
+
+A plain run measures the headline alone: W warm-up steps, a short probe of both launch modes (eager, replayed hipGraph), then
+K timed steps in the faster one (in the replayed hipGraph alone with --graph).  --dump-outputs DIR then writes what the last timed step returned to its caller -- every loss term, float64 -- as
+DIR/losses.<name>.npy.  --full adds everything else: both launch modes timed
+over the same K steps with the faster as the headline, the GEMM-family roofline, the same step in the other GEMM arithmetic
+modes (`alt_exact_f32`, `alt_bf16`), the CPU baseline, the data-pipeline rate, and at N = 1 `decode` (BASELINE configs[4]:
+5-shot KV-cached autoregressive decode at 512x512 with 68 support keypoints -- time per decode step, tokens/s, eager and
+replayed hipGraphs, against the weight-streaming roof) and `pck_check` (the same synthetic episode decoded by the product and
+by the CPU oracle: PCK@0.2 of both, token streams compared).  Blocks a run does not measure are null in the line.
 """
 import argparse
 import json
@@ -250,10 +261,18 @@ def main():
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_roofline", action="store_true")
     ap.add_argument("--graph", action="store_true",
-                    help="time only the hipGraph replay of the captured step (runtime/graph_step.py); by default at N = 1 both "
-                         "launch modes are timed over the same K steps and the faster one is the headline (both are reported)")
+                    help="time only the hipGraph replay of the captured step (runtime/graph_step.py); by default a plain run "
+                         "times the K steps in the launch mode that was faster over a short probe, and --full at N = 1 times "
+                         "both launch modes over the same K steps with the faster one as the headline (both are reported)")
     ap.add_argument("--no_decode", action="store_true", help="skip the configs[4] decode block and the PCK check")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement besides the headline (second launch mode, roofline, other GEMM "
+                         "arithmetic modes, CPU baseline, data pipeline, decode, PCK check); the --no_* switches prune it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the losses the last timed step returned as DIR/losses.<name>.npy (float64)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -293,8 +312,8 @@ def main():
     crit = crit.to(device)
     model.train()
     HF.Runtime.seed(1000 + rank, device)
-    opt = ArenaAdamW(model, lr=args.lr, lr_backbone=args.lr_backbone, weight_decay=args.weight_decay,
-                     max_norm=args.clip_max_norm)
+    # learning rate 0 (module docstring): same kernels and work per step, weights unchanged, losses reproducible run to run
+    opt = ArenaAdamW(model, lr=0.0, lr_backbone=0.0, weight_decay=args.weight_decay, max_norm=args.clip_max_norm)
     ddp = EpisodeDataParallel(model, opt) if world > 1 else None
     B, K = a.episodes, 2
     batches = make_batches(tok, B, K, a.image_size, 17, 4, seed=100 + rank, device=device)
@@ -303,33 +322,41 @@ def main():
     last = {}
 
     # the step can be captured after two eager calls and replayed (runtime/graph_step.py): one hipGraph at N = 1, two graphs
-    # around the bucket all-reduces under data parallelism; both launch modes are timed and the faster is the headline
+    # around the bucket all-reduces under data parallelism; --full times both launch modes and the faster is the headline
     state = {"gstep": None}
 
-    def step(i, eager=False):
+    def step(i, eager=False, keep=False):
+        """One training step; `keep`: hold on to its losses (detached) for --dump-outputs."""
         b = batches[i % len(batches)]
         gstep = state["gstep"]
         if gstep is not None and not eager:
-            last["loss"] = gstep(b["images"], b["support_coords"], b["support_mask"], b["targets"], b["skeleton"])["_total"]
+            losses = gstep(b["images"], b["support_coords"], b["support_mask"], b["targets"], b["skeleton"])
+            last["loss"] = losses["_total"]
+            if keep:
+                last["losses"] = losses
             return
         rng.advance()
         out = model(samples=b["images"], support_coords=b["support_coords"], support_mask=b["support_mask"],
                     targets=b["targets"], skeleton_edges=b["skeleton"])
-        total = crit(out, b["targets"])["_total"]
+        losses = crit(out, b["targets"])
+        total = losses["_total"]
         (total * scale).backward()
         if ddp is not None:
             ddp.finish()
         opt.step()
         opt.zero_grad()
         last["loss"] = total.detach()
+        if keep:                                 # detached: a live autograd graph would keep this step's activations alive
+            last["losses"] = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in losses.items()}
 
     def sync():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_region(label, warmup):
-        """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides."""
+    def timed_region(label, warmup, collect=False):
+        """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides; `collect`: also return
+        the losses the last of them returned to its caller, as float64 arrays."""
         for i in range(warmup):
             step(i)
             if i == 0:
@@ -339,29 +366,67 @@ def main():
         log(f"[{label}] timing {a.steps} steps")
         t0 = time.perf_counter()
         for i in range(a.steps):
-            step(warmup + i)
+            step(warmup + i, keep=collect and i == a.steps - 1)
         t_enq = time.perf_counter() - t0             # host time to enqueue the steps (launch-bound if ~ the timed region)
         sync()
         dt = time.perf_counter() - t0
-        t1 = time.perf_counter()
-        step(warmup + a.steps)                       # one step into an empty queue: pure host launch cost, no back-pressure
-        t_one = time.perf_counter() - t1
-        sync()
-        log(f"[{label}] host enqueue {t_enq / a.steps * 1e3:.2f} ms/step in the timed region; {t_one * 1e3:.2f} ms for one step "
-            f"into an empty queue; timed region {dt:.3f} s")
-        return {"dt": dt, "host_enqueue_ms_per_step": round(t_enq / a.steps * 1e3, 2), "host_ms_one_step": round(t_one * 1e3, 2),
-                "loss": float(last["loss"])}
+        res = {"dt": dt, "host_enqueue_ms_per_step": round(t_enq / a.steps * 1e3, 2), "host_ms_one_step": None,
+               "loss": float(last["loss"])}
+        if collect:
+            res["outputs"] = {f"losses.{k}": np.asarray(float(v), dtype=np.float64) for k, v in last.pop("losses").items()}
+        if a.full:
+            t1 = time.perf_counter()
+            step(warmup + a.steps)                   # one step into an empty queue: pure host launch cost, no back-pressure
+            res["host_ms_one_step"] = round((time.perf_counter() - t1) * 1e3, 2)
+            sync()
+        one = "" if res["host_ms_one_step"] is None else f"; {res['host_ms_one_step']:.2f} ms for one step into an empty queue"
+        log(f"[{label}] host enqueue {t_enq / a.steps * 1e3:.2f} ms/step in the timed region{one}; timed region {dt:.3f} s")
+        return res
 
     log(f"model built, {len(batches)} batches of {B} episodes resident; warm-up x{a.warmup}")
-    modes = {}
-    if not (world == 1 and a.graph):
-        modes["eager"] = timed_region("eager", a.warmup)
-    if world == 1 or os.environ.get("CAPE_BENCH_DP_GRAPH", "1") == "1":
+    from cape_amd.runtime.graph_step import GraphedTrainStep
+
+    def graph_step():
         # N > 1: the step as two captured graphs around the bucket all-reduces (runtime/graph_step.py, ddp=): exchange not
         # overlapped with the backward pass, host work ~2 replays + one collective call per bucket
-        from cape_amd.runtime.graph_step import GraphedTrainStep
-        state["gstep"] = GraphedTrainStep(model, crit, opt, loss_scale=scale, edge_capacity=2048, eager_steps=2, ddp=ddp)
-        modes["graph"] = timed_region("graph", max(a.warmup, 4))      # 2 eager calls + capture + first replay are warm-up
+        return GraphedTrainStep(model, crit, opt, loss_scale=scale, edge_capacity=2048, eager_steps=2, ddp=ddp)
+
+    def faster_mode(n=8):
+        """Both launch modes warmed up, then n steps of each between synchronizes: the faster one (eager while the host keeps
+        up with the GPU, the replayed graph when it does not).  The same steps run whichever mode wins."""
+        t = {}
+        for mode, warm in (("eager", max(a.warmup, 1)), ("graph", 4)):      # graph: 2 eager calls + capture + first replay
+            if mode == "graph":
+                state["gstep"] = graph_step()
+            for i in range(warm):
+                step(i)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(n):
+                step(i)
+            torch.cuda.synchronize()
+            t[mode] = time.perf_counter() - t0
+        best = min(sorted(t), key=lambda k: t[k])
+        if best != "graph":
+            state["gstep"] = None
+        log(f"launch-mode probe, {n} steps each: eager {t['eager'] / n * 1e3:.2f} ms/step, graph {t['graph'] / n * 1e3:.2f} ms/step -> {best}")
+        return best
+
+    # --full times both launch modes over the K steps and the faster is the headline; a plain run times the K steps once, in
+    # the mode that was faster over a short probe (N = 1), or in the one --graph names
+    collect = bool(a.dump_outputs) and rank == 0
+    probed = not a.full and world == 1 and not a.graph
+    if a.full:
+        run = [m for m, on in (("eager", not (world == 1 and a.graph)),
+                               ("graph", world == 1 or os.environ.get("CAPE_BENCH_DP_GRAPH", "1") == "1")) if on]
+    else:
+        run = [faster_mode()] if probed else ["graph" if a.graph else "eager"]
+    modes = {}
+    for mode in run:
+        if mode == "graph" and state["gstep"] is None:
+            state["gstep"] = graph_step()
+        warm = 0 if probed else (a.warmup if mode == "eager" else max(a.warmup, 4))
+        modes[mode] = timed_region(mode, warm, collect)
     if world > 1:                                # the slowest rank's time per mode: every rank then picks the same mode
         for k in sorted(modes):
             tt = torch.tensor([modes[k]["dt"]], dtype=torch.float64, device=device)
@@ -374,6 +439,11 @@ def main():
     log(f"headline launch mode: {best}; timed region {dt:.3f} s")
     loss = modes[best]["loss"]                   # the loss of the run that is reported (each mode's own is under launch_modes)
     assert all(np.isfinite(v["loss"]) for v in modes.values()), "non-finite loss in the bench"
+    if collect:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in modes[best]["outputs"].items():
+            np.save(os.path.join(a.dump_outputs, f"{name}.npy"), arr)
+        log(f"outputs of the last timed {best} step written to {a.dump_outputs}")
     episodes = B * world * a.steps
     value = episodes / dt
     ms_per_step = dt / a.steps * 1e3
@@ -388,7 +458,7 @@ def main():
                 "exposed_comm_ms_last_step": round(ddp.exposed_comm_ms(), 3)}
 
     roofline = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         # dominant kernel = the fp32-MFMA implicit-GEMM family (csrc/gemm.hip: gemm_kernel<...>): every launch of
         # the next steps is bracketed by HIP events on its own stream; achieved = sum(2MNK) / sum(duration)
         nprof = min(2, a.steps)
@@ -449,7 +519,7 @@ def main():
                     "avg_launch_us": round(avg_s * 1e6, 2),
                     "gemm_ms_per_step": round(r["ms"] / nprof, 2),
                     "gemm_gflop_per_step": round(r["flops"] / nprof / 1e9, 1)}
-    elif world > 1 and not a.no_roofline:
+    elif a.full and world > 1 and not a.no_roofline:
         for i in range(min(2, a.steps)):         # keep the collectives of the profiled steps matched on all ranks
             step(a.warmup + a.steps + i)
     if world > 1:
@@ -492,7 +562,7 @@ def main():
                              "algorithmic_bytes_per_launch": round(rf["bytes"] / max(rf["launches"], 1))}}
 
     alt, alt_bf16 = None, None
-    if world == 1 and not a.no_roofline and ops.get_gemm_precision() == "bf16x3":
+    if a.full and world == 1 and not a.no_roofline and ops.get_gemm_precision() == "bf16x3":
         alt = precision_leg("f32", both_modes=True)
         alt.update(gemm_precision="f32 (exact fp32 MFMA, v_mfma_f32_32x32x2_f32)")
         alt["roofline"]["kernel"] = "gemm_kernel / gemm_group_kernel <..., PREC 0>"
@@ -502,11 +572,11 @@ def main():
         alt_bf16["roofline"]["kernel"] = "gemm_rs_kernel / gemm_kernel / gemm_group_kernel, hi x hi product only"
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     datap = None
-    if rank == 0 and world == 1 and not a.no_decode:
+    if a.full and rank == 0 and world == 1 and not a.no_decode:
         try:
             datap = data_pipeline_benchmark(device)
             log(f"data_pipeline: {datap}")
@@ -515,7 +585,7 @@ def main():
             datap = {"error": f"{type(e).__name__}: {e}"}
 
     decode, pck = None, None
-    if rank == 0 and world == 1 and not a.no_decode:
+    if a.full and rank == 0 and world == 1 and not a.no_decode:
         # free the training state first: the decode model is a second instance (512x512, patch-2 input_proj)
         from cape_amd.runtime.decode_bench import decode_benchmark
         torch.cuda.synchronize()
@@ -543,7 +613,7 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32" if ops.get_gemm_precision() == "f32" else "f32 storage/accumulate, GEMMs as bf16x3 split (3 bf16 MFMAs per product)",
             "data": "synthetic",
-            "config": {"workload": f"configs[1]: 1-shot training step (fwd+loss+bwd+clip+AdamW, dropout on), "
+            "config": {"workload": f"configs[1]: 1-shot training step (fwd+loss+bwd+clip+AdamW at learning rate 0, dropout on), "
                                    f"{a.image_size}x{a.image_size}, 17 kpt, ResNet-50 + deformable transformer, "
                                    f"{B} episodes x 2 queries per GPU", "episodes_per_gpu": B, "queries_per_episode": K,
                        "image_size": a.image_size, "global_batch_episodes": B * world, "parallelism": f"dp{world}",

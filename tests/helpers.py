@@ -21,6 +21,26 @@ def build_product(extra=(), device="cuda", proc_sd=None):
     return args, tok, model.to(device), crit.to(device)
 
 
+def frozen(x, max_numel=4096):
+    """A nested batch / record (dicts, lists, tuples, tensors, arrays, scalars) in the form the reference fixtures store it
+    (oracle/make_golden_host.py): a tensor or array of more than `max_numel` elements becomes (type, shape, dtype, sha256 of its
+    bytes) -- still an exact comparison, at a few dozen bytes instead of the images themselves."""
+    import hashlib
+    import numpy as np
+    if isinstance(x, (torch.Tensor, np.ndarray)):
+        a = x.detach().cpu().contiguous().numpy() if isinstance(x, torch.Tensor) else np.ascontiguousarray(x)
+        if a.size <= max_numel:
+            return x.detach().cpu().clone() if isinstance(x, torch.Tensor) else a.copy()
+        return (type(x).__name__, tuple(a.shape), str(x.dtype), hashlib.sha256(a.tobytes()).hexdigest())
+    if isinstance(x, dict):
+        return {k: frozen(v, max_numel) for k, v in x.items()}
+    if isinstance(x, list):
+        return [frozen(v, max_numel) for v in x]
+    if isinstance(x, tuple):
+        return tuple(frozen(v, max_numel) for v in x)
+    return x
+
+
 def to_dev(batch, device="cuda"):
     out = dict(batch)
     for k in ("images", "support_coords", "support_mask"):

@@ -1,8 +1,8 @@
 """Host data path: the MP-100 loader, the episodic sampler / dataset and the transform plans, on a small
-COCO-style dataset written to a temp dir (PNG files + annotation JSON + category_splits.json).  Cross-checked against the
-reference's own `MP100CAPE` / `EpisodicDataset` classes (imported in place through oracle/refshim.py, with this package's
-pure-Python COCO reader standing in for pycocotools and the same deterministic transform callable) when the reference is
-present; the hand-computed checks run everywhere."""
+COCO-style dataset written to a temp dir (PNG files + annotation JSON + category_splits.json).  Cross-checked against what the
+reference's own `MP100CAPE` / `EpisodicDataset` classes returned on the same file set (tests/golden/mp100_records_ref.pth,
+written by oracle/make_golden_host.py with this package's pure-Python COCO reader standing in for pycocotools and the same
+deterministic transform callable), and by hand-computed checks."""
 import json
 import os
 import random
@@ -12,14 +12,13 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import refshim
-
 import cape_amd  # noqa: F401
 from cape_amd.datasets import (EpisodicDataset, ImageNotFoundError, MP100CAPE, build_episodic_dataloader, episodic_collate_fn)
 from cape_amd.datasets.coco_lite import COCO
 from cape_amd.datasets.transforms import HostTransform, apply_plan_host, images_from_raw_host, resize_plan, train_plan
+from tests.helpers import frozen
 
-needs_ref = pytest.mark.skipif(not refshim.reference_available(), reason="reference checkout not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 CATS = {1: 5, 2: 9, 3: 4}
 
@@ -169,59 +168,67 @@ def test_episodic_dataset_and_loader(tmp_path):
         assert torch.equal(b1["query_targets"][k], b2["query_targets"][k]), k
 
 
-def _ref_classes():
-    refshim.install()
-    import importlib
-    m = importlib.import_module("datasets.mp100_cape")
-    m.COCO = COCO                                   # pycocotools stand-in: this package's pure-Python reader
-    s = importlib.import_module("datasets.episodic_sampler")
-    return m, s
+RECORD_KEYS = ("image_id", "category_id", "num_keypoints", "num_visible_keypoints", "bbox", "bbox_width", "bbox_height", "height",
+               "width", "visibility", "skeleton")
+QUERY_META_KEYS = ("image_id", "height", "width", "num_keypoints", "num_visible_keypoints", "bbox", "bbox_width", "bbox_height",
+                   "visibility")
 
 
-@needs_ref
-def test_records_and_episodes_match_reference_classes(tmp_path):
-    ann = make_dataset(tmp_path)
-    m, s = _ref_classes()
+def records_and_episodes(root, ann, mp100_cls, episodic_cls, not_found_cls):
+    """What the cross-check compares, read through either implementation's classes from the file set of make_dataset(root):
+    every record (or "ImageNotFoundError"), then five fixed episodes (tests/helpers.frozen form)."""
     tr = HostTransform(train=False, size=64)
-    ref_ds = m.MP100CAPE(str(tmp_path / "data"), str(ann), tr, vocab_size=2000, seq_len=200)
-    ds = MP100CAPE(str(tmp_path / "data"), str(ann), tr, vocab_size=2000, seq_len=200)
-    assert ref_ds.ids == ds.ids and ref_ds.multi_instance_stats == ds.multi_instance_stats
+    ds = mp100_cls(str(root / "data"), str(ann), tr, vocab_size=2000, seq_len=200)
+    records = []
     for i in range(len(ds)):
         try:
-            want = ref_ds[i]
-        except m.ImageNotFoundError:
-            with pytest.raises(ImageNotFoundError):
-                ds[i]
+            r = ds[i]
+        except not_found_cls:
+            records.append("ImageNotFoundError")
             continue
-        got = ds[i]
-        for k in ("image_id", "category_id", "num_keypoints", "num_visible_keypoints", "bbox", "bbox_width", "bbox_height", "height",
-                  "width", "visibility", "skeleton"):
-            assert got[k] == want[k], (i, k)
-        assert np.allclose(np.array(got["keypoints"]), np.array(want["keypoints"]), atol=1e-9)
-        assert torch.equal(got["image"], want["image"])
-        for k in want["seq_data"]:
-            assert torch.equal(got["seq_data"][k], want["seq_data"][k].to(got["seq_data"][k].dtype)), (i, k)
+        records.append(frozen({**{k: r[k] for k in RECORD_KEYS}, "keypoints": np.array(r["keypoints"]), "image": r["image"],
+                               "seq_data": dict(r["seq_data"])}))
     # same seeds -> same episodes (python `random` drives the sampler in both)
-    split = str(tmp_path / "category_splits.json")
-    ref_ep = s.EpisodicDataset(ref_ds, split, split="train", num_queries_per_episode=2, num_support_per_episode=2, episodes_per_epoch=5, seed=11, fixed_episodes=True)
-    ep = EpisodicDataset(ds, split, split="train", num_queries_per_episode=2, num_support_per_episode=2, episodes_per_epoch=5, seed=11, fixed_episodes=True)
-    assert ref_ep._cached_episodes == ep._cached_episodes
+    ep = episodic_cls(ds, str(root / "category_splits.json"), split="train", num_queries_per_episode=2, num_support_per_episode=2,
+                      episodes_per_epoch=5, seed=11, fixed_episodes=True)
+    episodes = []
     for i in range(5):
         random.seed(100 + i)                    # a fixed episode with an unusable image falls back to random sampling
-        a = ref_ep[i]
-        random.seed(100 + i)
-        b = ep[i]
-        assert a["category_id"] == b["category_id"] and a["support_skeletons"] == b["support_skeletons"]
-        for x, y in zip(a["support_coords"], b["support_coords"]):
-            assert torch.equal(x, y)
-        for x, y in zip(a["support_masks"], b["support_masks"]):
-            assert torch.equal(x, y)
-        for x, y in zip(a["query_images"], b["query_images"]):
-            assert torch.equal(x, y)
-        for x, y in zip(a["query_metadata"], b["query_metadata"]):
-            for k in ("image_id", "height", "width", "num_keypoints", "num_visible_keypoints", "bbox", "bbox_width", "bbox_height", "visibility"):
-                assert x[k] == y[k], k
-        assert a["support_metadata"] == b["support_metadata"]
+        e = ep[i]
+        episodes.append(frozen({"category_id": e["category_id"], "support_skeletons": e["support_skeletons"],
+                                "support_coords": list(e["support_coords"]), "support_masks": list(e["support_masks"]),
+                                "query_images": list(e["query_images"]),
+                                "query_metadata": [{k: m[k] for k in QUERY_META_KEYS} for m in e["query_metadata"]],
+                                "support_metadata": e["support_metadata"]}))
+    return {"ids": list(ds.ids), "multi_instance_stats": ds.multi_instance_stats, "cached_episodes": ep._cached_episodes,
+            "records": records, "episodes": episodes}
+
+
+def test_records_and_episodes_match_reference_classes(tmp_path):
+    ann = make_dataset(tmp_path)
+    got = records_and_episodes(tmp_path, ann, MP100CAPE, EpisodicDataset, ImageNotFoundError)
+    want = torch.load(os.path.join(GOLDEN, "mp100_records_ref.pth"), weights_only=False)
+    assert want["ids"] == got["ids"] and want["multi_instance_stats"] == got["multi_instance_stats"]
+    assert len(want["records"]) == len(got["records"])
+    for i, (w, g) in enumerate(zip(want["records"], got["records"])):
+        if w == "ImageNotFoundError" or g == "ImageNotFoundError":
+            assert w == g, i
+            continue
+        for k in RECORD_KEYS + ("image",):
+            assert g[k] == w[k], (i, k)
+        assert np.allclose(g["keypoints"], w["keypoints"], atol=1e-9)
+        assert set(g["seq_data"]) == set(w["seq_data"])
+        for k in w["seq_data"]:
+            assert torch.equal(g["seq_data"][k], w["seq_data"][k].to(g["seq_data"][k].dtype)), (i, k)
+    assert want["cached_episodes"] == got["cached_episodes"]
+    for i, (a, b) in enumerate(zip(want["episodes"], got["episodes"])):
+        assert a["category_id"] == b["category_id"] and a["support_skeletons"] == b["support_skeletons"], i
+        for k in ("support_coords", "support_masks", "query_images"):
+            assert len(a[k]) == len(b[k]), (i, k)
+            for x, y in zip(a[k], b[k]):
+                assert (torch.equal(x, y) if isinstance(x, torch.Tensor) else x == y), (i, k)
+        assert a["query_metadata"] == b["query_metadata"] and a["support_metadata"] == b["support_metadata"], i
+    assert len(want["episodes"]) == len(got["episodes"]) == 5
 
 
 class _PlanProbe(torch.utils.data.Dataset):

@@ -1,19 +1,21 @@
 """Host-side contract of the path: the episodic collate (K-shot mean-pooling, padding,
-repeat per query) and the PCK evaluator, cross-checked against the reference's own functions when the reference is
-importable (the build container); on a machine without /root/reference the cross-checks skip and the golden-vector tests
-(tests/test_oracle_golden.py: tokenizer.npz, pck.npz) remain."""
+repeat per query), the PCK evaluator and the CLI flags, cross-checked against what the reference's own functions returned
+on the same inputs (tests/golden/collate_ref.pth, pck_evaluator_ref.json, cli_flags_ref.json, written by
+oracle/make_golden_host.py)."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
-
-from oracle import refshim
 
 import cape_amd  # noqa: F401
 from cape_amd.datasets import DiscreteTokenizerV2, episodic_collate_fn
 from cape_amd.datasets.synthetic import SyntheticEpisodes
 from cape_amd.util.eval_utils import PCKEvaluator, compute_pck_bbox
+from tests.helpers import frozen
 
-needs_ref = pytest.mark.skipif(not refshim.reference_available(), reason="reference checkout not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _same(a, b, path=""):
@@ -33,26 +35,25 @@ def _same(a, b, path=""):
         assert a == b, path
 
 
-@needs_ref
-@pytest.mark.parametrize("n_support", [1, 5])
-def test_collate_matches_reference(n_support):
-    """datasets/episodic_sampler.py:372-482: ragged keypoint counts across episodes, K-shot supports."""
-    refshim.install()
-    from datasets.episodic_sampler import episodic_collate_fn as ref_collate
+def collate_items(n_support):
+    """Four synthetic episodes with ragged keypoint counts: the inputs of collate_ref.pth."""
     tok = DiscreteTokenizerV2(44, 200)
     a = SyntheticEpisodes(tok, 4, 64, 9, 2, num_support=n_support, seed=4)
     b = SyntheticEpisodes(tok, 4, 64, 5, 2, num_support=n_support, seed=5)          # fewer keypoints: padding path
-    items = [a[0], b[1], a[2], b[3]]
-    _same(ref_collate(items), episodic_collate_fn(items))
+    return [a[0], b[1], a[2], b[3]]
 
 
-@needs_ref
-def test_pck_evaluator_matches_reference():
-    """util/eval_utils.py:29-260 on random predictions: tensors and lists, visibility 0/1/2, three categories."""
-    refshim.install()
-    from util.eval_utils import PCKEvaluator as RefEval
+@pytest.mark.parametrize("n_support", [1, 5])
+def test_collate_matches_reference(n_support):
+    """datasets/episodic_sampler.py:372-482: ragged keypoint counts across episodes, K-shot supports."""
+    want = torch.load(os.path.join(GOLDEN, "collate_ref.pth"), weights_only=False)[n_support]
+    _same(want, frozen(episodic_collate_fn(collate_items(n_support))))
+
+
+def pck_batches():
+    """Three batches of random predictions (tensors and ragged lists, visibility 0/1/2, three categories): the inputs of
+    pck_evaluator_ref.json."""
     rng = np.random.Generator(np.random.PCG64(9))
-    mine, ref = PCKEvaluator(0.2), RefEval(0.2)
     for it in range(3):
         B, P = 5, 11
         gt = torch.from_numpy(rng.random((B, P, 2)).astype(np.float32) * 200)
@@ -62,18 +63,33 @@ def test_pck_evaluator_matches_reference():
         cats = torch.from_numpy(rng.integers(1, 4, B))
         if it == 1:       # list form with ragged lengths
             lens = [P, 7, 3, P, 9]
-            args = ([pred[i, :n] for i, n in enumerate(lens)], [gt[i, :n] for i, n in enumerate(lens)], bw, bh, cats,
-                    [vis[i, :n] for i, n in enumerate(lens)])
+            yield ([pred[i, :n] for i, n in enumerate(lens)], [gt[i, :n] for i, n in enumerate(lens)], bw, bh, cats,
+                   [vis[i, :n] for i, n in enumerate(lens)])
         else:
-            args = (pred, gt, bw, bh, cats, vis)
+            yield (pred, gt, bw, bh, cats, vis)
+
+
+def pck_summary(ev):
+    """What the cross-check compares of an evaluator fed pck_batches(), in JSON types."""
+    r = ev.get_results()
+    return {"total_correct": int(r["total_correct"]), "total_visible": int(r["total_visible"]),
+            "categories": sorted(int(c) for c in r["pck_per_category"]),
+            "pck_overall": float(r["pck_overall"]), "mean_pck_categories": float(r["mean_pck_categories"]),
+            "num_correct": [int(x["num_correct"]) for x in ev.image_results]}
+
+
+def test_pck_evaluator_matches_reference():
+    """util/eval_utils.py:29-260 on random predictions: tensors and lists, visibility 0/1/2, three categories."""
+    mine = PCKEvaluator(0.2)
+    for args in pck_batches():
         mine.add_batch(*args)
-        ref.add_batch(*args)
-    rm, rr = mine.get_results(), ref.get_results()
+    rm = pck_summary(mine)
+    rr = json.load(open(os.path.join(GOLDEN, "pck_evaluator_ref.json")))
     assert rm["total_correct"] == rr["total_correct"] and rm["total_visible"] == rr["total_visible"]
-    assert rm["pck_per_category"].keys() == rr["pck_per_category"].keys()
+    assert rm["categories"] == rr["categories"]
     for k in ("pck_overall", "mean_pck_categories"):
         assert abs(rm[k] - rr[k]) < 1e-12
-    assert [r["num_correct"] for r in mine.image_results] == [r["num_correct"] for r in ref.image_results]
+    assert rm["num_correct"] == rr["num_correct"]
 
 
 def test_pck_edge_cases():
@@ -148,28 +164,26 @@ def test_optimizer_state_dict_interchanges_with_reference_adamw():
     assert torch.equal(opt.arenas[0].exp_avg, before)
 
 
-@needs_ref
+def cli_flag_table(parser):
+    """dest -> [option strings, action class, default, type name, choices, nargs], in JSON types (the form of
+    cli_flags_ref.json)."""
+    import argparse
+    out = {}
+    for a in parser._actions:
+        if isinstance(a, argparse._HelpAction):
+            continue
+        out[a.dest] = (tuple(a.option_strings), type(a).__name__, a.default, getattr(a.type, "__name__", a.type),
+                       tuple(a.choices) if a.choices else None, a.nargs)
+    return json.loads(json.dumps(out))
+
+
 def test_cli_parser_matches_reference_flag_by_flag():
     """`get_args_parser()` exposes the reference's flags with the same defaults / types / choices
     (`models/train_cape_episodic.py:86-254`); only `--dataset_root`'s author-specific default path and the added
     `synthetic` dataset name may differ."""
-    import argparse
     from cape_amd.models.train_cape_episodic import get_args_parser
-    refshim.install()
-    import importlib
-    ref = importlib.import_module("models.train_cape_episodic").get_args_parser()
-    ours = get_args_parser()
-
-    def table(parser):
-        out = {}
-        for a in parser._actions:
-            if isinstance(a, argparse._HelpAction):
-                continue
-            out[a.dest] = (tuple(a.option_strings), type(a).__name__, a.default, getattr(a.type, "__name__", a.type),
-                           tuple(a.choices) if a.choices else None, a.nargs)
-        return out
-
-    t_ref, t_ours = table(ref), table(ours)
+    t_ref = json.load(open(os.path.join(GOLDEN, "cli_flags_ref.json")))
+    t_ours = cli_flag_table(get_args_parser())
     assert set(t_ref) <= set(t_ours), f"flags missing here: {sorted(set(t_ref) - set(t_ours))}"
     allowed_default_diff = {"dataset_root"}
     for k, v in t_ref.items():

@@ -32,7 +32,7 @@ def main():
         f = fams.setdefault(fam(r["Name"]), [0, 0])
         f[0] += int(r["Calls"]); f[1] += int(r["TotalDurationNs"])
     g = fams["GEMM family (gemm_kernel + gemm_rs_kernel + gemm_group_kernel)"]
-    out = [f"# rocprofv3 --kernel-trace --stats of `python3 bench.py --steps 4 --warmup 2 --no_cpu_baseline --no_decode --no_roofline`",
+    out = [f"# rocprofv3 --kernel-trace --stats of `python3 bench.py --full --steps 4 --warmup 2 --no_cpu_baseline --no_decode --no_roofline`",
            f"# (tools/profile_round.sh), {steps} training steps in the trace (eager and hipGraph legs: warm-up + timed + host-cost probes)",
            f"all kernels: {calls} launches, {tot / 1e6:.1f} ms = {tot / steps / 1e6:.2f} ms of kernel time per step, {calls / steps:.0f} launches per step"]
     for k, (c, t) in sorted(fams.items(), key=lambda kv: -kv[1][1]):
