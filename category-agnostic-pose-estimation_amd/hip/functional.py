@@ -4,6 +4,7 @@ Each `torch.autograd.Function` here is glue: forward and backward only *launch* 
 libcape_hip.so (through `ops`) and keep the tensors backward needs.  No arithmetic of the hot path is
 done by torch ops in this file.
 """
+import contextlib
 import ctypes
 import os
 
@@ -32,13 +33,14 @@ class Runtime:
     # Weight gradients are not launched where the backward pass produces them: nothing waits for one until the optimizer
     # step, so their GEMM descriptors are queued (per tile class) and submitted `wgrad_group` at a time as ONE grouped launch
     # (csrc/gemm_group.hip) -- and whatever is left when the autograd engine finishes the pass.  Round 2 paid 199 launches,
-    # 24-64 k-splits each to fill the chip alone, for what is now ~15 launches of 4-8 k-splits.
+    # 24-64 k-splits each to fill the chip alone, for what is now ~15 launches of 4-8 k-splits.  Two products of one group never
+    # write overlapping bytes (items with split_k == 1 add into C without atomics): such a product launches the queued class first.
     defer_wgrad = os.environ.get("CAPE_DEFER_WGRAD", "1") == "1"
     wgrad_group = int(os.environ.get("CAPE_WGRAD_GROUP", "12"))
-    wq = {}                      # (tile, b_mode, precision) -> [(desc, keep, shape)]
+    wq = {}                      # (tile, b_mode, precision) -> [(desc, keep, shape, destination byte ranges)]
     wq_total = 0
     wq_notify = []               # parameters whose notification (data-parallel bucket bookkeeping) waits for the queued products
-    _final_cb = False
+    _final_cb = False            # the end-of-pass flush is registered with the running backward pass
 
     @classmethod
     def side_stream(cls):
@@ -68,25 +70,26 @@ class Runtime:
                     cb(p)
 
     @classmethod
-    def enqueue_wgrad(cls, desc, keep, shape):
-        M, N, K, _, b_mode = shape
+    def enqueue_wgrad(cls, desc, keep):
+        M, N, K, b_mode = desc.M, desc.N, desc.K, desc.b_mode
         key = (ops.group_tile(M, N, K), b_mode, desc.precision)
-        cls.wq.setdefault(key, []).append((desc, keep, shape))
+        dst = [(desc.C, desc.C + 4 * ((M - 1) * desc.ldc + N))]
+        if desc.colsum_out:
+            dst.append((desc.colsum_out, desc.colsum_out + 4 * M))
+        items = cls.wq.setdefault(key, [])
+        if any(lo < e and s < hi for it in items for s, e in it[3] for lo, hi in dst):
+            cls._launch_class(key)                      # (the same weight again, e.g. a layer applied twice): its group goes first
+        cls.wq[key].append((desc, keep, (M, N, K, 1, b_mode), dst))
         cls.wq_total += 1
         if not cls._final_cb:
             try:                                        # whatever is still queued when this backward pass ends goes then
-                torch.autograd.Variable._execution_engine.queue_callback(cls._on_backward_end)
+                torch.autograd.Variable._execution_engine.queue_callback(cls.flush_wgrads)
                 cls._final_cb = True
             except RuntimeError:                        # not inside a backward pass (a Function driven by hand): no deferral
                 cls.flush_wgrads()
                 return
         if cls.wq_total >= cls.wgrad_group or len(cls.wq[key]) >= lib.GEMM_GROUP_MAX:
-            cls.flush_wgrads()
-
-    @classmethod
-    def _on_backward_end(cls):
-        cls._final_cb = False
-        cls.flush_wgrads()
+            cls._flush()
 
     @classmethod
     def _launch_class(cls, key):
@@ -99,26 +102,19 @@ class Runtime:
         shapes = [it[2] for it in items]
         for it, sk in zip(items, ops.plan_group_splits([sh[:3] for sh in shapes], tile)):
             it[0].split_k = sk
-        keep = [t for it in items for t in it[1] if t is not None]
-        side = cls.use_side_stream
-        if side:                                        # ordered after everything the main stream has been given so far
-            cls.side_stream()
-            lib.call("cape_stream_fork", ctypes.c_void_p(ops.raw_current_stream()), ctypes.c_void_p(cls.side_raw))
-            cls.side_dirty = True
-            ops._stream_override[0] = cls.side_raw
-        try:
+        with _Side([t for it in items for t in it[1]]):
             for i in range(0, len(items), lib.GEMM_GROUP_MAX):
                 ops.gemm_group([it[0] for it in items[i:i + lib.GEMM_GROUP_MAX]], shapes[i:i + lib.GEMM_GROUP_MAX], tile)
-        finally:
-            if side:
-                ops._stream_override[0] = None
-        if side:
-            (cls.capture_keep if cls.capture_keep is not None else cls.pending).extend(keep)
 
     @classmethod
     def flush_wgrads(cls):
         """Launch every queued weight-gradient product (one grouped launch per tile class) and run the notifications
-        that waited for them."""
+        that waited for them.  The next queued product registers a new end-of-pass flush (also after a pass that raised)."""
+        cls._final_cb = False
+        cls._flush()
+
+    @classmethod
+    def _flush(cls):
         for key in list(cls.wq):
             cls._launch_class(key)
         if cls.wq_notify:
@@ -138,13 +134,6 @@ class Runtime:
         cls.rng = ops.RngState(int(seed), device)
 
 
-def _mark_side_dirty():
-    Runtime.side_dirty = True
-
-
-ops._on_fork[0] = _mark_side_dirty
-
-
 def capturing():
     """True while the current stream is being captured into a hipGraph: host decisions that would need a
     device->host sync take their conservative branch, and cross-stream lifetimes are handled by keeping tensors alive."""
@@ -155,23 +144,97 @@ def _c(t):
     return t if (t is None or t.is_contiguous()) else t.contiguous()
 
 
-def _sink(p):
-    """Gradient-arena view of parameter `p` (or of the parameter `p` is a plain view of), else None."""
-    if not Runtime.direct_grad or p is None or not p.requires_grad:
+class _Side:
+    """Context of side-stream work: kernels launched inside go to the side stream, ordered after the current stream's work so far (one C
+    call at the block's first launch: event record + wait; no framework stream switch); the tensors are kept alive until the next
+    join -- the caching allocator may otherwise hand their blocks to a later main-stream kernel while the side kernel still reads
+    them.  Blocks nest (a group launched from inside a node's block)."""
+
+    def __init__(self, tensors):
+        self.tensors = [t for t in tensors if t is not None]
+
+    def __enter__(self):
+        self.on, self.forked, self.prev = Runtime.use_side_stream, False, ops._side[0]
+        if self.on:
+            Runtime.side_stream()
+            ops._side[0] = self._raw
+        return self
+
+    def _raw(self):
+        if not self.forked:                             # (a block whose products are all queued launches nothing: no fork)
+            self.forked = True
+            lib.call("cape_stream_fork", ctypes.c_void_p(ops.raw_current_stream()), ctypes.c_void_p(Runtime.side_raw))
+            Runtime.side_dirty = True
+        return Runtime.side_raw
+
+    def __exit__(self, *a):
+        if not self.on:
+            return False
+        ops._side[0] = self.prev
+        (Runtime.capture_keep if Runtime.capture_keep is not None else Runtime.pending).extend(self.tensors)
+        if len(Runtime.pending) > 8192:                 # a caller that never joins (backward without an optimizer step)
+            Runtime.join()
+        return False
+
+
+def _groupable(d):
+    """A weight-gradient product that cape_gemm_group_f32 takes: C += A^T B (dense or im2col B) with at most the fused bias sums,
+    on the vector path of the tile body (16-byte aligned operands and rows)."""
+    return (d.a_mode == 1 and d.accumulate and d.b_mode in (1, 3) and d.batch == 0 and d.mask_src is None and d.bias is None
+            and d.A % 16 == 0 and d.B % 16 == 0 and d.lda % 4 == 0 and d.M % 4 == 0 and d.M >= 4 and d.N % 4 == 0 and d.N >= 4
+            and (d.b_mode == 3 or d.ldb % 4 == 0) and max(d.lda, d.ldb, d.ldc) < (1 << 31))
+
+
+_NO_SIDE = contextlib.nullcontext()
+
+
+class _ParamGrads:
+    """Where the parameter gradients of one node backward go.  `bufs[i]` receives the gradient of refs[i] (None when it needs none):
+      * direct -- EVERY parameter the node must differentiate owns a gradient-arena view (runtime/arena.py): the kernels accumulate
+        into those views (inside side(): on the side stream; wgrad products issued through gemm() join the deferred groups,
+        Runtime.defer_wgrad); result() notifies each parameter once and hands autograd Nones;
+      * otherwise fresh zero tensors (the parameter's layout: a channels_last conv weight stays channels_last), written on the main
+        stream and returned by result().  All or nothing: a side-stream kernel never writes a tensor that autograd reads.
+    needs: per ref, whether it is differentiated (default: every ref that is not None)."""
+
+    def __init__(self, refs, needs=None):
+        self.refs = refs
+        self.needs = [r is not None and (needs is None or bool(needs[i])) for i, r in enumerate(refs)]
+        views = [self._view(r) if n else None for r, n in zip(refs, self.needs)]
+        self.direct = any(self.needs) and all(v is not None for v, n in zip(views, self.needs) if n)
+        self.bufs = views if self.direct else [torch.zeros_like(r) if n else None for r, n in zip(refs, self.needs)]
+
+    @staticmethod
+    def _view(p):
+        """Gradient-arena view of parameter `p` (or of the parameter `p` is a plain view of), else None."""
+        if not Runtime.direct_grad or not p.requires_grad:
+            return None
+        if isinstance(p, torch.nn.Parameter):
+            return p.grad
+        base = p._base
+        if isinstance(base, torch.nn.Parameter) and base.grad is not None and base.requires_grad:
+            off = p.storage_offset() - base.storage_offset() + base.grad.storage_offset()
+            return torch.as_strided(base.grad, p.shape, p.stride(), off)
         return None
-    if isinstance(p, torch.nn.Parameter):
-        return p.grad
-    base = p._base
-    if isinstance(base, torch.nn.Parameter) and base.grad is not None and base.requires_grad:
-        off = p.storage_offset() - base.storage_offset() + base.grad.storage_offset()
-        return torch.as_strided(base.grad, p.shape, p.stride(), off)
-    return None
 
+    def side(self, *tensors):
+        """Context of the node's side-stream work (may be entered more than once); a no-op unless direct.  `tensors`: what it reads."""
+        return _Side(tensors) if self.direct else _NO_SIDE
 
-def _param_of(p):
-    if isinstance(p, torch.nn.Parameter):
-        return p
-    return p._base if (p is not None and isinstance(p._base, torch.nn.Parameter)) else None
+    def gemm(self, *args, **kw):
+        """A weight-gradient product (ops.gemm arguments): queued for a grouped launch when direct and deferring, else launched."""
+        d, keep = ops.gemm_desc(*args, **kw)
+        if self.direct and Runtime.defer_wgrad and _groupable(d):
+            Runtime.enqueue_wgrad(d, keep)
+        else:
+            ops.launch_gemm(d)
+
+    def result(self):
+        """The node's return values for refs: the fresh gradients, or Nones after one notification per differentiated parameter."""
+        if not self.direct:
+            return tuple(self.bufs)
+        Runtime.notify(*[r if isinstance(r, torch.nn.Parameter) else r._base for r, n in zip(self.refs, self.needs) if n])
+        return (None,) * len(self.refs)
 
 
 class _Slot:
@@ -209,46 +272,6 @@ def _slot_offer(slot, buf):
         slot.buf = buf
 
 
-class _Side:
-    """with _Side(tensors...): kernels launched inside go to the side stream, ordered after the current stream's work so far
-    (one C call: event record + wait; no framework stream switch); the listed tensors are kept alive until the next join --
-    the caching allocator may otherwise hand their blocks to a later main-stream kernel while the side kernel still reads them."""
-
-    def __init__(self, *tensors):
-        self.tensors = [t for t in tensors if t is not None]
-
-    def __enter__(self):
-        self.on = Runtime.use_side_stream
-        self.defer = Runtime.defer_wgrad
-        if self.defer:
-            ops._wgrad_sink[0] = self._sink
-        if not self.on:
-            return self
-        Runtime.side_stream()
-        ops._stream_override[0] = Runtime.side_raw
-        if self.defer:
-            ops._lazy_fork[0] = True                    # queued products need no fork here; any other launch orders the stream first
-        else:
-            lib.call("cape_stream_fork", ctypes.c_void_p(ops.raw_current_stream()), ctypes.c_void_p(Runtime.side_raw))
-            Runtime.side_dirty = True
-        return self
-
-    def _sink(self, desc, keep, shape):
-        # the queue keeps the product's operands alive until its launch; on a capture nothing is ever released
-        Runtime.enqueue_wgrad(desc, keep, shape)
-
-    def __exit__(self, *a):
-        ops._wgrad_sink[0] = None
-        if not self.on:
-            return False
-        ops._stream_override[0] = None
-        ops._lazy_fork[0] = False
-        (Runtime.capture_keep if Runtime.capture_keep is not None else Runtime.pending).extend(self.tensors)
-        if len(Runtime.pending) > 8192:                 # a caller that never joins (backward without an optimizer step)
-            Runtime.join()
-        return False
-
-
 # ------------------------------------------------------------------------------------------------
 # Linear (+bias, +relu, +dropout, +residual) -- F.linear and its autograd
 # ------------------------------------------------------------------------------------------------
@@ -280,33 +303,21 @@ class LinearFn(torch.autograd.Function):
         if relu or p > 0:
             assert relu, "dropout epilogue is only used together with relu"
             dpre = ops.relu_drop_bwd(dy2, y, 1.0 / (1.0 - p) if p > 0 else 1.0)
-        dx = dw = db = dres = None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx, acc = _grad_target(ctx.slot, (M, K), dy.device)
             ops.gemm(dpre, weight, dx, M, K, N, a_mode=0, b_mode=1, ldb=weight.stride(0), accumulate=acc)
             dx = dx.view(xshape)
-        wsink, bsink = _sink(ctx.w_ref), _sink(ctx.b_ref)
-        need_w, need_b = ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
-        if (need_w and wsink is not None) or (need_b and bsink is not None):
-            with _Side(dpre, x2):
-                fuse_b = need_b and bsink is not None and need_w and wsink is not None   # bias sums ride in the wgrad
-                if need_w and wsink is not None:
-                    ops.gemm(dpre, x2, wsink, N, K, M, a_mode=1, b_mode=1, lda=N, ldb=K, ldc=wsink.stride(0), accumulate=True,
-                             split_k=ops.pick_split_k(N, K, M), colsum_out=bsink if fuse_b else None)
-                if need_b and bsink is not None and not fuse_b:
-                    ops.colsum(dpre, M, N, bsink)
-            Runtime.notify(_param_of(ctx.w_ref) if (need_w and wsink is not None) else None,
-                           _param_of(ctx.b_ref) if (need_b and bsink is not None) else None)
-        if need_w and wsink is None:
-            dw = torch.zeros(N, K, dtype=torch.float32, device=dy.device)
-            ops.gemm(dpre, x2, dw, N, K, M, a_mode=1, b_mode=1, lda=N, ldb=K, accumulate=True,
-                     split_k=ops.pick_split_k(N, K, M))
-        if need_b and bsink is None:
-            db = torch.zeros(N, dtype=torch.float32, device=dy.device)
-            ops.colsum(dpre, M, N, db)
-        if has_res and ctx.needs_input_grad[3]:
-            dres = dy
-        return dx, dw, db, dres, None, None, None
+        pg = _ParamGrads((ctx.w_ref, ctx.b_ref), ctx.needs_input_grad[1:3])
+        dw, db = pg.bufs
+        with pg.side(dpre, x2):
+            if dw is not None:                          # the bias sums ride in the wgrad
+                pg.gemm(dpre, x2, dw, N, K, M, a_mode=1, b_mode=1, lda=N, ldb=K, ldc=dw.stride(0), accumulate=True,
+                        split_k=ops.pick_split_k(N, K, M), colsum_out=db)
+            elif db is not None:
+                ops.colsum(dpre, M, N, db)
+        dres = dy if (has_res and ctx.needs_input_grad[3]) else None
+        return (dx,) + pg.result() + (dres, None, None, None)
 
 
 def linear(x, weight, bias=None, residual=None, relu=False, dropout_p=0.0, rng_stream=0):
@@ -347,21 +358,14 @@ class FFNFn(torch.autograd.Function):
             dx, acc = _grad_target(ctx.slot, (M, K), dy.device)
             ops.gemm(dpre, w1, dx, M, K, Hd, a_mode=0, b_mode=1, ldb=w1.stride(0), accumulate=acc)
             dx = dx.view(xshape)
-        sinks = [_sink(t) for t in ctx.refs]
-        if all(k is not None for k in sinks) and all(ctx.needs_input_grad[1:5]):
-            with _Side(dy2, dpre, h, x2):
-                ops.gemm(dy2, h, sinks[2], N, Hd, M, a_mode=1, b_mode=1, lda=N, ldb=Hd, ldc=sinks[2].stride(0), accumulate=True,
-                         split_k=ops.pick_split_k(N, Hd, M), colsum_out=sinks[3])
-                ops.gemm(dpre, x2, sinks[0], Hd, K, M, a_mode=1, b_mode=1, lda=Hd, ldb=K, ldc=sinks[0].stride(0), accumulate=True,
-                         split_k=ops.pick_split_k(Hd, K, M), colsum_out=sinks[1])
-            Runtime.notify(*[_param_of(t) for t in ctx.refs])
-            return dx, None, None, None, None, None, None
-        dev = dy.device
-        dw2 = torch.zeros(N, Hd, dtype=torch.float32, device=dev); db2 = torch.zeros(N, dtype=torch.float32, device=dev)
-        dw1 = torch.zeros(Hd, K, dtype=torch.float32, device=dev); db1 = torch.zeros(Hd, dtype=torch.float32, device=dev)
-        ops.gemm(dy2, h, dw2, N, Hd, M, a_mode=1, b_mode=1, lda=N, ldb=Hd, accumulate=True, split_k=ops.pick_split_k(N, Hd, M), colsum_out=db2)
-        ops.gemm(dpre, x2, dw1, Hd, K, M, a_mode=1, b_mode=1, lda=Hd, ldb=K, accumulate=True, split_k=ops.pick_split_k(Hd, K, M), colsum_out=db1)
-        return dx, dw1, db1, dw2, db2, None, None
+        pg = _ParamGrads(ctx.refs)
+        dw1, db1, dw2, db2 = pg.bufs
+        with pg.side(dy2, dpre, h, x2):
+            pg.gemm(dy2, h, dw2, N, Hd, M, a_mode=1, b_mode=1, lda=N, ldb=Hd, ldc=dw2.stride(0), accumulate=True,
+                    split_k=ops.pick_split_k(N, Hd, M), colsum_out=db2)
+            pg.gemm(dpre, x2, dw1, Hd, K, M, a_mode=1, b_mode=1, lda=Hd, ldb=K, ldc=dw1.stride(0), accumulate=True,
+                    split_k=ops.pick_split_k(Hd, K, M), colsum_out=db1)
+        return (dx,) + pg.result() + (None, None)
 
 
 _NO_FFN_FUSE = os.environ.get("CAPE_NO_FFN_FUSE") is not None
@@ -424,27 +428,17 @@ class LinearCat2Fn(torch.autograd.Function):
             ops.gemm(dy2, w1, dx, M, K, N1, a_mode=0, b_mode=1, lda=NT)
             ops.gemm(dy2[:, N1:], w2, dx, M, K, N2, a_mode=0, b_mode=1, lda=NT, accumulate=True)
             dx = dx.view(xshape)
-        sinks = [_sink(t) for t in ctx.refs]
-        if all(k is not None for k in sinks):
-            with _Side(dy2, x2):
-                if adjacent and _adjacent(sinks[0], sinks[2]) and _adjacent(sinks[1], sinks[3]):      # the gradients mirror the layout
-                    ops.gemm(dy2, x2, torch.as_strided(sinks[0], (NT, K), (K, 1)), NT, K, M, a_mode=1, b_mode=1, lda=NT, accumulate=True,
-                             split_k=ops.pick_split_k(NT, K, M), colsum_out=torch.as_strided(sinks[1], (NT,), (1,)))
-                else:
-                    ops.gemm(dy2, x2, sinks[0], N1, K, M, a_mode=1, b_mode=1, lda=NT, accumulate=True, split_k=ops.pick_split_k(N1, K, M),
-                             colsum_out=sinks[1])
-                    ops.gemm(dy2[:, N1:], x2, sinks[2], N2, K, M, a_mode=1, b_mode=1, lda=NT, accumulate=True,
-                             split_k=ops.pick_split_k(N2, K, M), colsum_out=sinks[3])
-            Runtime.notify(*[_param_of(t) for t in ctx.refs])
-            return dx, None, None, None, None
-        dw1 = torch.zeros(N1, K, dtype=torch.float32, device=dev)
-        dw2 = torch.zeros(N2, K, dtype=torch.float32, device=dev)
-        ops.gemm(dy2, x2, dw1, N1, K, M, a_mode=1, b_mode=1, lda=NT, accumulate=True, split_k=ops.pick_split_k(N1, K, M))
-        ops.gemm(dy2[:, N1:], x2, dw2, N2, K, M, a_mode=1, b_mode=1, lda=NT, accumulate=True,
-                 split_k=ops.pick_split_k(N2, K, M))
-        db = torch.zeros(NT, dtype=torch.float32, device=dev)
-        ops.colsum(dy2, M, NT, db)
-        return dx, dw1, db[:N1], dw2, db[N1:]
+        pg = _ParamGrads(ctx.refs)
+        dw1, db1, dw2, db2 = pg.bufs
+        with pg.side(dy2, x2):
+            if adjacent and _adjacent(dw1, dw2) and _adjacent(db1, db2):      # the gradients mirror the layout: one product
+                pg.gemm(dy2, x2, torch.as_strided(dw1, (NT, K), (K, 1)), NT, K, M, a_mode=1, b_mode=1, lda=NT, accumulate=True,
+                        split_k=ops.pick_split_k(NT, K, M), colsum_out=torch.as_strided(db1, (NT,), (1,)))
+            else:
+                for dw, db, lo, n in ((dw1, db1, 0, N1), (dw2, db2, N1, N2)):
+                    pg.gemm(dy2[:, lo:], x2, dw, n, K, M, a_mode=1, b_mode=1, lda=NT, accumulate=True, split_k=ops.pick_split_k(n, K, M),
+                            colsum_out=db)
+        return (dx,) + pg.result()
 
 
 def linear_cat2(x, w1, b1, w2, b2):
@@ -532,38 +526,23 @@ class ConvFn(torch.autograd.Function):
                     dx.zero_()
                 ops.gemm(dpre, wp, dx, N * H * W, C, KH * KW * O, a_mode=3, b_mode=2, conv=geom, split_k=sk,
                          accumulate=sk > 1 or acc_dx is not None)
-        wsink = _sink(ctx.w_ref)
-        ssink = _sink(ctx.shift_ref) if (has_shift and ctx.needs_input_grad[3]) else None
-        need_w = ctx.needs_input_grad[1]
-        need_s = has_shift and ctx.needs_input_grad[3]
+        # the weight gradient is computed in the physical (O, KH, KW, C) layout of the channels_last weight (and of its gradient)
+        pg = _ParamGrads((ctx.w_ref, ctx.shift_ref), (ctx.needs_input_grad[1], has_shift and ctx.needs_input_grad[3]))
+        dw, dshift = pg.bufs
         src_s = None
-        if need_s:
+        if dshift is not None:
             src_s = dpre if scale is None else (dres if dres is not None else _mask_only(dy, y, relu))
-
-        def wgrad(dst_phys, bias_sums=None):
-            if dense:
-                ops.gemm(dpre, x, dst_phys, O, C, M, a_mode=1, b_mode=1, lda=O, ldb=C, accumulate=True,
-                         split_k=ops.pick_split_k(O, C, M), colsum_out=bias_sums)
-            else:
-                ops.gemm(dpre, x, dst_phys, O, K, M, a_mode=1, b_mode=3, lda=O, conv=geom, accumulate=True,
-                         split_k=ops.pick_split_k(O, K, M), colsum_out=bias_sums)
-
-        if (need_w and wsink is not None) or (need_s and ssink is not None):
-            with _Side(dpre, x, src_s):
-                fuse_s = need_s and ssink is not None and need_w and wsink is not None and src_s is dpre
-                if need_w and wsink is not None:
-                    wgrad(_w_phys(wsink), ssink if fuse_s else None)
-                if need_s and ssink is not None and not fuse_s:
-                    ops.colsum(src_s, M, O, ssink)
-            Runtime.notify(_param_of(ctx.w_ref) if (need_w and wsink is not None) else None,
-                           _param_of(ctx.shift_ref) if (need_s and ssink is not None) else None)
-        if need_w and wsink is None:
-            dwp = torch.zeros(O, KH, KW, C, dtype=torch.float32, device=dy.device)
-            wgrad(dwp)
-            dw = dwp.permute(0, 3, 1, 2)
-        if need_s and ssink is None:
-            dshift = torch.zeros(O, dtype=torch.float32, device=dy.device)
-            ops.colsum(src_s, M, O, dshift)
+        with pg.side(dpre, x, src_s):
+            fuse_s = src_s is dpre and dw is not None   # the bias sums ride in the wgrad
+            if dw is not None:
+                kw = dict(a_mode=1, lda=O, accumulate=True, colsum_out=dshift if fuse_s else None)
+                if dense:
+                    pg.gemm(dpre, x, _w_phys(dw), O, C, M, b_mode=1, ldb=C, split_k=ops.pick_split_k(O, C, M), **kw)
+                else:
+                    pg.gemm(dpre, x, _w_phys(dw), O, K, M, b_mode=3, conv=geom, split_k=ops.pick_split_k(O, K, M), **kw)
+            if dshift is not None and not fuse_s:
+                ops.colsum(src_s, M, O, dshift)
+        dw, dshift = pg.result()
         return dx, dw, None, dshift, dres, None, None, None, None
 
 
@@ -737,21 +716,14 @@ class AddLayerNormFn(torch.autograd.Function):
         if d_out is None:
             d_out, d_out_pos = d_out_pos, None
         d_out, d_out_pos = _c(d_out), _c(d_out_pos)
-        C = x.shape[-1]
-        gs, bs = _sink(ctx.refs[0]), _sink(ctx.refs[1])
-        direct = gs is not None and bs is not None
-        dg = gs if direct else torch.zeros(C, dtype=torch.float32, device=x.device)
-        db = bs if direct else torch.zeros(C, dtype=torch.float32, device=x.device)
+        pg = _ParamGrads(ctx.refs)
         rng = Runtime.get_rng(x.device) if p > 0 else None
-        dx, dy = ops.add_layernorm_bwd(d_out, d_out_pos, x, y, gamma, mean, rstd, dg, db, dropout_p=p, rng=rng,
+        dx, dy = ops.add_layernorm_bwd(d_out, d_out_pos, x, y, gamma, mean, rstd, *pg.bufs, dropout_p=p, rng=rng,
                                        rng_stream=stream)
         if y is None or dy is not dx:               # (without dropout the kernel hands ONE buffer to x and y: not exclusively x's)
             _slot_offer(ctx.slot, dx)
-        if direct:
-            Runtime.notify(_param_of(ctx.refs[0]), _param_of(ctx.refs[1]))
-            dg = db = None
         dpos = g_pos if (has_pos and ctx.needs_input_grad[4]) else None
-        return dx, (dy if y is not None else None), dg, db, dpos, None, None
+        return (dx, (dy if y is not None else None)) + pg.result() + (dpos, None, None)
 
 
 def add_layernorm(x, y, gamma, beta, pos=None, dropout_p=0.0, rng_stream=0):
@@ -778,27 +750,28 @@ class FanOutFn(torch.autograd.Function):
     write).  Gradients that autograd reports as None (an unused alias) are skipped."""
 
     @staticmethod
-    def forward(ctx, x, k):
-        ctx.k = k
+    def forward(ctx, x, k, slot):
+        ctx.k, ctx.slot = k, slot
         ctx.set_materialize_grads(False)
         return tuple(x.view_as(x) for _ in range(k))
 
     @staticmethod
     def backward(ctx, *grads):
+        ctx.slot.buf = None                                  # every consumer has run: a later pass (retain_graph) starts afresh
         gs, seen = [], set()
         for g in grads:                                      # consumers that accumulated into the slot's buffer report it more than once
             if g is not None and (g.data_ptr(), g.numel()) not in seen:
                 seen.add((g.data_ptr(), g.numel()))
                 gs.append(g)
         if not gs:
-            return None, None
+            return None, None, None
         if len(gs) > 1 and len(gs) <= 8 and not all(g.is_contiguous() for g in gs) and all(_row_strided(g) for g in gs):
-            return ops.add_n_rows(gs), None                  # a summand is a column block of a wider buffer: summed where it lies
+            return ops.add_n_rows(gs), None, None            # a summand is a column block of a wider buffer: summed where it lies
         gs = [_c(g) for g in gs]
         out = gs[0]
         for i in range(0, len(gs) - 1, 7):                  # 8 sources per launch
             out = ops.add_n([out] + gs[1 + i:8 + i]) if len(gs) > 1 else out
-        return out, None
+        return out, None, None
 
 
 def _row_strided(g):
@@ -812,8 +785,8 @@ def fanout(x, k):
     """k aliases of x whose gradients are summed by one HIP launch (no-op outside autograd or for k == 1)."""
     if k == 1 or not (torch.is_grad_enabled() and x.requires_grad):
         return (x,) * k
-    outs = FanOutFn.apply(x, k)
     slot = _Slot()
+    outs = FanOutFn.apply(x, k, slot)
     for o in outs:
         o._cape_slot = slot                                  # consumers find the shared gradient slot on their input (see _Slot)
     return outs
@@ -858,13 +831,9 @@ class ScaleResidualFn(torch.autograd.Function):
         dx = g if ctx.has_x else None
         if gamma is None:
             return dx, g, None
-        sink = _sink(ctx.gref)
-        dgamma = sink if sink is not None else torch.zeros_like(gamma)
-        dy = ops.scale_residual_bwd(g, y, gamma, dgamma)
-        if sink is not None:
-            Runtime.notify(_param_of(ctx.gref))
-            dgamma = None
-        return dx, dy, dgamma
+        pg = _ParamGrads((ctx.gref,))
+        dy = ops.scale_residual_bwd(g, y, gamma, pg.bufs[0])
+        return (dx, dy) + pg.result()
 
 
 def scale_residual(x, y, gamma=None):
@@ -971,15 +940,10 @@ class LevelGroupNormFn(torch.autograd.Function):
         dxs, dgs, dbs = [], [], []
         for l in range(L):
             h, w = geo.shapes[l]
-            gs, bs = _sink(ctx.refs[0][l]), _sink(ctx.refs[1][l])
-            direct = gs is not None and bs is not None
-            dg = gs if direct else torch.zeros(C, dtype=torch.float32, device=d_out.device)
-            db = bs if direct else torch.zeros(C, dtype=torch.float32, device=d_out.device)
-            dx = ops.groupnorm_bwd(d_out[:, geo.starts[l]:], S * C, xs[l], gammas[l], st[2 * l], st[2 * l + 1], dg, db, N,
+            pg = _ParamGrads((ctx.refs[0][l], ctx.refs[1][l]))
+            dx = ops.groupnorm_bwd(d_out[:, geo.starts[l]:], S * C, xs[l], gammas[l], st[2 * l], st[2 * l + 1], *pg.bufs, N,
                                    h * w, C)
-            if direct:
-                Runtime.notify(_param_of(ctx.refs[0][l]), _param_of(ctx.refs[1][l]))
-                dg = db = None
+            dg, db = pg.result()
             dxs.append(dx); dgs.append(dg); dbs.append(db)
         return (None, *dxs, *dgs, *dbs)
 
@@ -1027,15 +991,11 @@ class LevelPosFn(torch.autograd.Function):
         geo, N = ctx.geo, ctx.N
         d_pos = _c(d_pos)
         C = d_pos.shape[-1]
-        sink = _sink(ctx.le_ref)
-        d_le = sink if sink is not None else torch.zeros(geo.L, C, dtype=torch.float32, device=d_pos.device)
+        pg = _ParamGrads((ctx.le_ref,))
         for l in range(geo.L):
             h, w = geo.shapes[l]
-            ops.colsum(d_pos[0, geo.starts[l]:], h * w, C, d_le[l], nbatch=N, batch_stride=geo.S * C)
-        if sink is not None:
-            Runtime.notify(_param_of(ctx.le_ref))
-            d_le = None
-        return (None, d_le) + (None,) * geo.L
+            ops.colsum(d_pos[0, geo.starts[l]:], h * w, C, pg.bufs[0][l], nbatch=N, batch_stride=geo.S * C)
+        return (None,) + pg.result() + (None,) * geo.L
 
 
 def level_pos(geo, level_embed, masks_u8):
@@ -1129,22 +1089,11 @@ class MHAFn(torch.autograd.Function):
         Mq, Mk = N * Lq, N * Lk
         dO = torch.empty(Mq, C, dtype=torch.float32, device=dev)
         ops.gemm(d_out2, out_w, dO, Mq, C, C, a_mode=0, b_mode=1)
-        sinks = [_sink(t) for t in ctx.refs]
-        direct = all(k is not None for k in sinks)
-        d_out_w = sinks[2] if direct else torch.zeros(C, C, dtype=torch.float32, device=dev)
-        d_out_b = sinks[3] if direct else torch.zeros(C, dtype=torch.float32, device=dev)
-        d_in_w = sinks[0] if direct else torch.zeros(3 * C, C, dtype=torch.float32, device=dev)
-        d_in_b = sinks[1] if direct else torch.zeros(3 * C, dtype=torch.float32, device=dev)
-
-        def out_grads():
-            ops.gemm(d_out2, O.view(-1, C), d_out_w, C, C, Mq, a_mode=1, b_mode=1, accumulate=True,
-                     split_k=ops.pick_split_k(C, C, Mq), colsum_out=d_out_b)
-
-        if direct:
-            with _Side(d_out2, O):
-                out_grads()
-        else:
-            out_grads()
+        pg = _ParamGrads(ctx.refs)
+        d_in_w, d_in_b, d_out_w, d_out_b = pg.bufs
+        with pg.side(d_out2, O):
+            pg.gemm(d_out2, O.view(-1, C), d_out_w, C, C, Mq, a_mode=1, b_mode=1, accumulate=True,
+                    split_k=ops.pick_split_k(C, C, Mq), colsum_out=d_out_b)
         if merged == 3:                              # gradients in the layout of the wide projection result
             dqkv = torch.empty(N, Lq, 3 * C, dtype=torch.float32, device=dev)
             dq, dk, dv = dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]
@@ -1162,28 +1111,21 @@ class MHAFn(torch.autograd.Function):
             ops.attn_bwd(dO.view(N, Lq, C), q, k, v, O, lse, dq, dk, dv, N, nheads, Lq, Lk, scale, mask_mode=mask_mode, kpm=kpm,
                          dropout_p=p, rng=rng, rng_stream=stream)
 
-        def in_grads():
+        with pg.side(dq, dk, dv, q_in, k_in, v_in):
             if merged == 3:                          # [dq | dk | dv]^T x: one product for the stacked in_proj rows
-                ops.gemm(dqkv.view(-1, 3 * C), q_in.view(-1, C), d_in_w, 3 * C, C, Mq, a_mode=1, b_mode=1, lda=3 * C, accumulate=True,
-                         split_k=ops.pick_split_k(3 * C, C, Mq), colsum_out=d_in_b)
-                return
-            ops.gemm(dq.view(-1, C), q_in.view(-1, C), d_in_w, C, C, Mq, a_mode=1, b_mode=1, accumulate=True,
-                     split_k=ops.pick_split_k(C, C, Mq), colsum_out=d_in_b)
+                pg.gemm(dqkv.view(-1, 3 * C), q_in.view(-1, C), d_in_w, 3 * C, C, Mq, a_mode=1, b_mode=1, lda=3 * C, accumulate=True,
+                        split_k=ops.pick_split_k(3 * C, C, Mq), colsum_out=d_in_b)
+            else:
+                pg.gemm(dq.view(-1, C), q_in.view(-1, C), d_in_w, C, C, Mq, a_mode=1, b_mode=1, accumulate=True,
+                        split_k=ops.pick_split_k(C, C, Mq), colsum_out=d_in_b)
             if merged == 2:
-                ops.gemm(dkv.view(-1, 2 * C), k_in.view(-1, C), d_in_w[C:], 2 * C, C, Mk, a_mode=1, b_mode=1, lda=2 * C, accumulate=True,
-                         split_k=ops.pick_split_k(2 * C, C, Mk), colsum_out=d_in_b[C:])
-                return
-            for i, (g, src, M) in ((1, (dk, k_in, Mk)), (2, (dv, v_in, Mk))):
-                ops.gemm(g.view(-1, C), src.view(-1, C), d_in_w[i * C:], C, C, M, a_mode=1, b_mode=1, accumulate=True,
-                         split_k=ops.pick_split_k(C, C, M), colsum_out=d_in_b[i * C:])
-
-        if direct:
-            with _Side(dq, dk, dv, q_in, k_in, v_in):
-                in_grads()
-            Runtime.notify(*[_param_of(t) for t in ctx.refs])
-            d_in_w = d_in_b = d_out_w = d_out_b = None
-        else:
-            in_grads()
+                pg.gemm(dkv.view(-1, 2 * C), k_in.view(-1, C), d_in_w[C:], 2 * C, C, Mk, a_mode=1, b_mode=1, lda=2 * C, accumulate=True,
+                        split_k=ops.pick_split_k(2 * C, C, Mk), colsum_out=d_in_b[C:])
+            elif merged == 0:
+                for i, g, src in ((1, dk, k_in), (2, dv, v_in)):
+                    pg.gemm(g.view(-1, C), src.view(-1, C), d_in_w[i * C:], C, C, Mk, a_mode=1, b_mode=1, accumulate=True,
+                            split_k=ops.pick_split_k(C, C, Mk), colsum_out=d_in_b[i * C:])
+        d_in_w, d_in_b, d_out_w, d_out_b = pg.result()
         # input gradients; when the same tensor came in as k and v (support features) or as q, k and v (self-attention of the
         # support encoder) the products accumulate into ONE buffer (GEMM epilogue C += ...) and the duplicates report None
         dq_in = dk_in = dv_in = None
@@ -1278,11 +1220,6 @@ class DecSelfAttnFn(torch.autograd.Function):
         M = N * L
         dev = d_out.device
         d_out2 = _c(d_out).view(M, C)
-        sinks = [_sink(t) for t in ctx.refs]
-        direct = all(k is not None for k in sinks)
-        g = (lambda i, shape: sinks[i] if direct else torch.zeros(shape, dtype=torch.float32, device=dev))
-        d_wq, d_wk, d_wv = g(0, (C, C)), g(1, (C, C)), g(2, (C, C))
-        d_in_w, d_in_b, d_out_w, d_out_b = g(3, (3 * C, C)), g(4, (3 * C,)), g(5, (C, C)), g(6, (C,))
         dO = torch.empty(M, C, dtype=torch.float32, device=dev)
         ops.gemm(d_out2, out_w, dO, M, C, C, a_mode=0, b_mode=1)
         dqkv2 = torch.empty(N, L, 3 * C, dtype=torch.float32, device=dev)
@@ -1310,26 +1247,19 @@ class DecSelfAttnFn(torch.autograd.Function):
                 for i, w in enumerate((wq, wk, wv)):
                     ops.gemm(dqkv1[:, i * C:], w, dx, M, C, C, a_mode=0, b_mode=1, lda=3 * C, accumulate=acc or i > 0)
 
-        def wgrads():
+        pg = _ParamGrads(ctx.refs)
+        d_wq, d_wk, d_wv, d_in_w, d_in_b, d_out_w, d_out_b = pg.bufs
+        with pg.side(d_out2, O, dqkv2, qkv1, dqkv1, x):
             Mv = dqkv2.view(M, 3 * C)
-            ops.gemm(d_out2, O.view(M, C), d_out_w, C, C, M, a_mode=1, b_mode=1, accumulate=True, split_k=ops.pick_split_k(C, C, M),
-                     colsum_out=d_out_b)
+            pg.gemm(d_out2, O.view(M, C), d_out_w, C, C, M, a_mode=1, b_mode=1, accumulate=True, split_k=ops.pick_split_k(C, C, M),
+                    colsum_out=d_out_b)
             for i, dw in enumerate((d_wq, d_wk, d_wv)):
-                ops.gemm(Mv[:, i * C:], qkv1[:, i * C:], d_in_w[i * C:], C, C, M, a_mode=1, b_mode=1, lda=3 * C, ldb=3 * C, accumulate=True,
-                         split_k=ops.pick_split_k(C, C, M), colsum_out=d_in_b[i * C:])
-                ops.gemm(dqkv1[:, i * C:], x, dw, C, C, M, a_mode=1, b_mode=1, lda=3 * C, ldb=C, accumulate=True,
-                         split_k=ops.pick_split_k(C, C, M))
-
-        if direct:
-            with _Side(d_out2, O, dqkv2, qkv1, dqkv1, x):
-                wgrads()
-            Runtime.notify(*[_param_of(t) for t in ctx.refs])
-            grads = (None,) * 7
-        else:
-            wgrads()
-            grads = (d_wq, d_wk, d_wv, d_in_w, d_in_b, d_out_w, d_out_b)
+                pg.gemm(Mv[:, i * C:], qkv1[:, i * C:], d_in_w[i * C:], C, C, M, a_mode=1, b_mode=1, lda=3 * C, ldb=3 * C, accumulate=True,
+                        split_k=ops.pick_split_k(C, C, M), colsum_out=d_in_b[i * C:])
+                pg.gemm(dqkv1[:, i * C:], x, dw, C, C, M, a_mode=1, b_mode=1, lda=3 * C, ldb=C, accumulate=True,
+                        split_k=ops.pick_split_k(C, C, M))
         dpos = dqkv1[:, :C].view(N, L, C) if need_pos else None      # (a row-strided view of the wide gradient)
-        return (dx, dpos) + grads + (None, None, None)
+        return (dx, dpos) + pg.result() + (None, None, None)
 
 
 def dec_self_attn(tgt, pos, wq, wk, wv, in_w, in_b, out_w, out_b, nheads=8, dropout_p=0.0, rng_stream=0):
@@ -1359,13 +1289,9 @@ class TokenEmbedFn(torch.autograd.Function):
     def backward(ctx, d_out):
         sv = ctx.saved_tensors
         tshape, pad_idx = ctx.meta
-        sink = _sink(ctx.t_ref)
-        d_table = sink if sink is not None else torch.zeros(tshape, dtype=torch.float32, device=d_out.device)
-        ops.token_embed_bwd(_c(d_out).view(-1, tshape[1]), sv[:4], sv[4:], d_table, pad_idx if pad_idx is not None else -1)
-        if sink is not None:
-            Runtime.notify(_param_of(ctx.t_ref))
-            d_table = None
-        return (d_table,) + (None,) * 9
+        pg = _ParamGrads((ctx.t_ref,))
+        ops.token_embed_bwd(_c(d_out).view(-1, tshape[1]), sv[:4], sv[4:], pg.bufs[0], pad_idx if pad_idx is not None else -1)
+        return pg.result() + (None,) * 9
 
 
 def token_embed(table, pad_idx, s11, s21, s12, s22, dx1, dx2, dy1, dy2):
@@ -1473,15 +1399,9 @@ class SupportEmbedFn(torch.autograd.Function):
             return None, None, None, None
         h, coords = ctx.saved_tensors
         N, P, C = ctx.meta
-        ws, bs = _sink(ctx.refs[0]), _sink(ctx.refs[1])
-        direct = ws is not None and bs is not None
-        dW = ws if direct else torch.zeros(C, 2, dtype=torch.float32, device=h.device)
-        db = bs if direct else torch.zeros(C, dtype=torch.float32, device=h.device)
-        ops.support_embed_bwd(_c(d_h).view(-1, C), h, coords, dW, db, N, P, C)
-        if direct:
-            Runtime.notify(_param_of(ctx.refs[0]), _param_of(ctx.refs[1]))
-            dW = db = None
-        return None, dW, db, None
+        pg = _ParamGrads(ctx.refs)
+        ops.support_embed_bwd(_c(d_h).view(-1, C), h, coords, *pg.bufs, N, P, C)
+        return (None,) + pg.result() + (None,)
 
 
 def support_embed(coords, W0, b0, pe1d):

@@ -20,10 +20,7 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _raw_device = getattr(torch._C, "_cuda_getDevice", None)
 
 
-_stream_override = [None]        # set by hip/functional._Side: launches go to the weight-gradient side stream
-_lazy_fork = [False]             # the side stream has not yet been ordered after the main stream for the current _Side block
-_on_fork = [None]                # callback of hip/functional.Runtime: the side stream now holds work that a join must wait for
-_wgrad_sink = [None]             # callable(desc, keep, shape) while weight-gradient products are being queued (Runtime.defer_wgrad)
+_side = [None]                   # set by hip/functional._Side: callable -> hipStream_t of the side stream (ordered on first use)
 
 
 def raw_current_stream():
@@ -36,13 +33,8 @@ def _stream():
     """hipStream_t of torch's current stream on the current device (or the side stream while hip/functional._Side is active).  The two private C entry points cost ~0.5 us; the public
     torch.cuda.current_stream().cuda_stream walks Python helpers for ~8 us -- 40 % of a launcher's host time, ~6 ms per
     training step (1250 launches)."""
-    if _stream_override[0] is not None:
-        if _lazy_fork[0]:           # first launch of a _Side block that queues its weight gradients: order the side stream now
-            _lazy_fork[0] = False
-            lib.call("cape_stream_fork", ctypes.c_void_p(raw_current_stream()), ctypes.c_void_p(_stream_override[0]))
-            if _on_fork[0] is not None:
-                _on_fork[0]()
-        return ctypes.c_void_p(_stream_override[0])
+    if _side[0] is not None:
+        return ctypes.c_void_p(_side[0]())
     if _raw_stream is not None and _raw_device is not None:
         return ctypes.c_void_p(_raw_stream(_raw_device()))
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -262,10 +254,16 @@ class PackedWeights:
         cls.entries, cls._table = {}, None
 
 
-def gemm(A, B, C, M, N, K, a_mode=0, b_mode=0, lda=None, ldb=None, ldc=None, bias=None, scale=None, residual=None,
-         ldr=None, relu=False, accumulate=False, split_k=1, dropout_p=0.0, rng=None, rng_stream=0, conv=None,
-         colsum_out=None, packed=None, mask_src=None, mask_scale=1.0, batch=None, res_cols=0, bias_strides=None, conv_sub=None):
-    """packed: the B operand as fragment-ordered bf16 planes (PackedWeights / cape_pack_weights); looked up automatically when B
+def gemm(*args, **kw):
+    """C = op(A) op(B) [epilogue]: gemm_desc(...) launched at once on the current stream."""
+    launch_gemm(gemm_desc(*args, **kw)[0])
+
+
+def gemm_desc(A, B, C, M, N, K, a_mode=0, b_mode=0, lda=None, ldb=None, ldc=None, bias=None, scale=None, residual=None,
+              ldr=None, relu=False, accumulate=False, split_k=1, dropout_p=0.0, rng=None, rng_stream=0, conv=None,
+              colsum_out=None, packed=None, mask_src=None, mask_scale=1.0, batch=None, res_cols=0, bias_strides=None, conv_sub=None):
+    """The checked lib.GemmDesc of one product and the tensors it reads or writes (which must outlive its launch).
+    packed: the B operand as fragment-ordered bf16 planes (PackedWeights / cape_pack_weights); looked up automatically when B
     is a parameter (or a view of one) and the product is one the register-stationary kernel takes."""
     for t, n in ((A, "A"), (B, "B"), (C, "C"), (bias, "bias"), (scale, "scale"), (residual, "residual")):
         _chk(t, "gemm." + n, contiguous=False)
@@ -346,27 +344,23 @@ def gemm(A, B, C, M, N, K, a_mode=0, b_mode=0, lda=None, ldb=None, ldc=None, bia
         assert _avail(bias) >= N
     if scale is not None:
         assert scale.numel() >= N
-    if (_wgrad_sink[0] is not None and a_mode == 1 and accumulate and batch is None and mask_src is None and bias is None
-            and b_mode in (1, 3) and _group_ok(d)):
-        _wgrad_sink[0](d, (A, B, C, colsum_out), (M, N, K, a_mode, b_mode))      # queued: launched with its group (gemm_group)
-        return
+    return d, (A, B, C, colsum_out)
+
+
+def launch_gemm(d):
+    """One cape_gemm_f32 launch of a gemm_desc descriptor (timed with HIP events while GemmProfiler is on)."""
     if GemmProfiler.enabled:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         st = _stream()
-        e0.record(torch.cuda.ExternalStream(st.value) if _stream_override[0] is not None else None)
+        ext = torch.cuda.ExternalStream(st.value) if _side[0] is not None else None
+        e0.record(ext)
         lib.call("cape_gemm_f32", ctypes.byref(d), st)
-        e1.record(torch.cuda.ExternalStream(st.value) if _stream_override[0] is not None else None)
-        nb = batch[0] if batch is not None else 1
-        GemmProfiler.records.append((e0, e1, 2.0 * M * N * K * nb, (M, N, K, a_mode, b_mode, int(split_k), nb),
+        e1.record(ext)
+        M, N, K, nb = d.M, d.N, d.K, max(d.batch, 1)
+        GemmProfiler.records.append((e0, e1, 2.0 * M * N * K * nb, (M, N, K, d.a_mode, d.b_mode, d.split_k, nb),
                                      GemmProfiler.alg_bytes(M, N, K, nb), 1))
         return
     lib.call("cape_gemm_f32", ctypes.byref(d), _stream())
-
-
-def _group_ok(d):
-    """The conditions of cape_gemm_group_f32 (vector path of the tile body) for one weight-gradient product."""
-    return (d.A % 16 == 0 and d.B % 16 == 0 and d.lda % 4 == 0 and d.M % 4 == 0 and d.M >= 4 and d.N % 4 == 0 and d.N >= 4
-            and (d.b_mode == 3 or d.ldb % 4 == 0) and max(d.lda, d.ldb, d.ldc) < (1 << 31))
 
 
 _AUTO_SPLIT_NN = os.environ.get("CAPE_AUTO_SPLIT_NN", "1") == "1" and os.environ.get("CAPE_DETERMINISTIC", "0") != "1"
@@ -406,7 +400,7 @@ def gemm_group(descs, shapes, tile):
     if GemmProfiler.enabled:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         st = _stream()
-        ext = torch.cuda.ExternalStream(st.value) if _stream_override[0] is not None else None
+        ext = torch.cuda.ExternalStream(st.value) if _side[0] is not None else None
         e0.record(ext)
         lib.call("cape_gemm_group_f32", arr, n, tile, st)
         e1.record(ext)

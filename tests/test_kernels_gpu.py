@@ -1033,28 +1033,24 @@ def test_decoder_self_attention_node_matches_the_chain_of_nodes():
 
 @pytest.mark.parametrize("prec", ["bf16x3", "f32"])
 @pytest.mark.parametrize("tile", [64, 128])
-def test_gemm_group_dense_wgrads(prec, tile):
+def test_gemm_group_dense_wgrad_descs(prec, tile):
     """cape_gemm_group_f32: several weight-gradient products (different shapes, k-splits, with / without fused bias sums, ragged K)
     in ONE launch == the same products one by one on the CPU.  Destinations start non-zero: the group accumulates."""
-    from cape_amd.hip import lib
+    from cape_amd.hip import functional as HF
     cases = [(256, 256, 6400, 4, True), (768, 256, 544, 1, True), (384, 256, 3000, 8, False), (68, 36, 100, 1, True),
              (1024, 256, 2050, 2, True), (256, 1024, 640, 3, False), (132, 260, 40, 1, False)]
     old = ops.get_gemm_precision()
     try:
         ops.set_gemm_precision(prec)
         descs, shapes, keep, refs = [], [], [], []
-        sink = lambda d, k, sh: (descs.append(d), keep.append(k), shapes.append(sh))
         for i, (Mo, Ni, Kr, sk, cs) in enumerate(cases):
             dy, x = rnd(Kr, Mo, seed=10 + i), rnd(Kr, Ni, seed=30 + i)
             out = torch.full((Mo, Ni), 0.5, device=DEV)
             csum = torch.full((Mo,), 2.0, device=DEV) if cs else None
-            ops._wgrad_sink[0] = sink
-            try:
-                ops.gemm(dy.to(DEV), x.to(DEV), out, Mo, Ni, Kr, a_mode=1, b_mode=1, accumulate=True, split_k=sk, colsum_out=csum)
-            finally:
-                ops._wgrad_sink[0] = None
+            d, k = ops.gemm_desc(dy.to(DEV), x.to(DEV), out, Mo, Ni, Kr, a_mode=1, b_mode=1, accumulate=True, split_k=sk, colsum_out=csum)
+            assert HF._groupable(d)                          # the backward pass would queue this product
+            descs.append(d); keep.append(k); shapes.append((Mo, Ni, Kr, 1, 1))
             refs.append((out, 0.5 + dy.t() @ x, csum, 2.0 + dy.sum(0)))
-        assert len(descs) == len(cases)                      # every product was queued, none launched
         ops.gemm_group(descs, shapes, tile)
     finally:
         ops.set_gemm_precision(old)
@@ -1069,11 +1065,11 @@ def test_gemm_group_dense_wgrads(prec, tile):
         ops.gemm_group(descs * 5, shapes * 5, tile)          # 35 items > CAPE_GEMM_GROUP_MAX
 
 
-def test_gemm_group_conv_wgrads():
+def test_gemm_group_conv_wgrad_descs():
     """Grouped im2col weight gradients (b_mode 3) of different geometries against F.conv2d's autograd."""
     geoms = [(2, 16, 16, 64, 64, 3, 1, 1), (2, 17, 15, 32, 48, 3, 2, 1), (2, 32, 32, 4, 64, 7, 2, 3), (1, 8, 8, 256, 256, 3, 2, 1)]
+    from cape_amd.hip import functional as HF
     descs, shapes, keep, refs = [], [], [], []
-    sink = lambda d, k, sh: (descs.append(d), keep.append(k), shapes.append(sh))
     for i, (N, H, W, C, O, k, stride, pad) in enumerate(geoms):
         x, w, geom, OH, OW = _conv_case(N, H, W, C, O, k, stride, pad, seed=50 + i)
         w.requires_grad_(True)
@@ -1083,11 +1079,9 @@ def test_gemm_group_conv_wgrads():
         xn = x.permute(0, 2, 3, 1).contiguous().to(DEV)
         gn = g.permute(0, 2, 3, 1).contiguous().to(DEV)
         dw = torch.zeros(O, k * k * C, device=DEV)
-        ops._wgrad_sink[0] = sink
-        try:
-            ops.gemm(gn, xn, dw, O, k * k * C, N * OH * OW, a_mode=1, b_mode=3, lda=O, conv=geom, accumulate=True, split_k=1)
-        finally:
-            ops._wgrad_sink[0] = None
+        d, kp = ops.gemm_desc(gn, xn, dw, O, k * k * C, N * OH * OW, a_mode=1, b_mode=3, lda=O, conv=geom, accumulate=True, split_k=1)
+        assert HF._groupable(d)
+        descs.append(d); keep.append(kp); shapes.append((O, k * k * C, N * OH * OW, 1, 3))
         refs.append((dw.view(O, k, k, C), w.grad.permute(0, 2, 3, 1)))
     for d, sk in zip(descs, ops.plan_group_splits([sh[:3] for sh in shapes], 64)):
         d.split_k = sk
@@ -1181,6 +1175,111 @@ def test_deferred_weight_gradients_match_immediate_launches():
         for i, (g, r) in enumerate(zip(got, ref)):
             close(g, r, tol=2e-4, name=f"deferred grad {i} (group {group})")
             assert float(r.abs().max()) > 0
+
+
+def _arena_runtime(monkeypatch, **kw):
+    """hip/functional.Runtime as ArenaAdamW sets it up (gradients straight into .grad), for one test."""
+    from cape_amd.hip import functional as HF
+    monkeypatch.setattr(HF.Runtime, "direct_grad", True)
+    for k, v in kw.items():
+        monkeypatch.setattr(HF.Runtime, k, v)
+    return HF
+
+
+def test_grouped_weight_gradients_never_share_a_destination(monkeypatch):
+    """A weight used twice in one pass puts two products onto one .grad: they must not land in one grouped launch (a split_k == 1
+    item adds into C without atomics, so two blocks of one grid would race).  With a group size that would otherwise hold the
+    whole pass, every launched group has disjoint destinations and the gradients equal one launch per product."""
+    torch.manual_seed(5)
+    ws = [torch.nn.Parameter(torch.randn(256, 256, device=DEV) * 0.06) for _ in range(4)]
+    bs = [torch.nn.Parameter(torch.randn(256, device=DEV) * 0.1) for _ in range(4)]
+    params = ws + bs
+    x = torch.randn(4, 200, 256, device=DEV)
+    order = [0, 1, 2, 3, 0]                                  # w0 again after three other products
+
+    def ranges(d):
+        r = [(d.C, d.C + 4 * ((d.M - 1) * d.ldc + d.N))]
+        return r + ([(d.colsum_out, d.colsum_out + 4 * d.M)] if d.colsum_out else [])
+
+    launched = []
+    real_group = ops.gemm_group
+
+    def checked_group(descs, shapes, tile):
+        rs = [r for d in descs for r in ranges(d)]
+        for i, (s0, e0) in enumerate(rs):
+            for s1, e1 in rs[i + 1:]:
+                assert not (s0 < e1 and s1 < e0), "one grouped launch writes overlapping destinations"
+        launched.append(len(descs))
+        return real_group(descs, shapes, tile)
+
+    def run(defer):
+        HF = _arena_runtime(monkeypatch, defer_wgrad=defer, wgrad_group=32)
+        for p in params:
+            p.grad = torch.zeros_like(p)
+        h = x
+        for i in order:
+            h = HF.linear(h, ws[i], bs[i], relu=True)
+        h.square().mean().backward()
+        HF.Runtime.join()
+        torch.cuda.synchronize()
+        assert HF.Runtime.wq_total == 0
+        return [p.grad.clone() for p in params]
+
+    monkeypatch.setattr(ops, "gemm_group", checked_group)
+    ref = run(False)
+    assert not launched
+    got = run(True)
+    assert sum(launched) == len(order) and len(launched) >= 2
+    for i, (g, r) in enumerate(zip(got, ref)):
+        close(g, r, tol=2e-4, name=f"grad {i} of a weight used twice")
+        assert float(r.abs().max()) > 0
+
+
+def test_gradient_slot_is_fresh_for_every_pass(monkeypatch):
+    """A fan-out's gradient slot holds the first consumer's buffer for the others to add into; a second backward over the retained
+    graph must not find the previous pass's buffer there (it would add onto it)."""
+    HF = _arena_runtime(monkeypatch)
+    torch.manual_seed(2)
+    C = 256
+    w, b = torch.nn.Parameter(torch.randn(C, C, device=DEV) * 0.06), torch.nn.Parameter(torch.zeros(C, device=DEV))
+    g1, be1 = torch.nn.Parameter(torch.ones(C, device=DEV)), torch.nn.Parameter(torch.zeros(C, device=DEV))
+    for p in (w, b, g1, be1):
+        p.grad = torch.zeros_like(p)
+    x = torch.randn(3, 200, C, device=DEV, requires_grad=True)
+    go = torch.randn(3, 200, C, device=DEV)
+    u, v = HF.fanout(x, 2)
+    y = HF.add_layernorm(u, HF.linear(v, w, b), g1, be1)
+    y.backward(go, retain_graph=True)
+    first = x.grad.clone()
+    x.grad = None
+    y.backward(go)
+    HF.Runtime.join()
+    close(x.grad, first.cpu(), tol=1e-6, name="input gradient of the second pass")
+    assert float(first.abs().max()) > 0
+
+
+def test_end_of_pass_flush_survives_a_failed_backward(monkeypatch):
+    """A backward that raises (here from a tensor hook) after queuing weight gradients never reaches its end-of-pass callback.
+    After join() the next pass must register its own flush: its queued products are launched when backward() returns."""
+    HF = _arena_runtime(monkeypatch, defer_wgrad=True, wgrad_group=12)
+    torch.manual_seed(4)
+    ws = [torch.nn.Parameter(torch.randn(256, 256, device=DEV) * 0.06) for _ in range(2)]
+    for p in ws:
+        p.grad = torch.zeros_like(p)
+    x = torch.randn(2, 100, 256, device=DEV, requires_grad=True)
+
+    def fail(g):
+        raise RuntimeError("hook failure")
+
+    h = HF.linear(x, ws[0])
+    h.register_hook(fail)
+    with pytest.raises(RuntimeError, match="hook failure"):
+        HF.linear(h, ws[1]).sum().backward()                # ws[1]'s product is queued, then the hook raises
+    HF.Runtime.join()
+    assert HF.Runtime.wq_total == 0
+    HF.linear(HF.linear(x, ws[0]), ws[1]).sum().backward()  # 2 products < wgrad_group: only the end-of-pass flush launches them
+    assert HF.Runtime.wq_total == 0
+    HF.Runtime.join()
 
 
 # ------------------------------------------------------------------------------------------------
