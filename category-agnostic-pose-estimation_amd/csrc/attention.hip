@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
     const int last_row = min(p.Lq - 1, blockIdx.x * ROWS + ((threadIdx.x | 63) >> 2));
     jend = min(p.Lk, last_row + p.causal_offset + 1);
   }
-  const uint8_t* kp = p.mask_mode == 2 ? p.kpm + (long long)n * p.Lk : nullptr;
+  const uint8_t* kp = p.mask_mode >= 2 ? p.kpm + (long long)n * p.Lk : nullptr;
   const uint64_t rbase = (((uint64_t)n * p.H + h) * p.Lq + (uint64_t)(live ? i : 0)) * p.Lk;
   for (int k0 = 0; k0 < p.Lk; k0 += MAXL) {
     const int kc = min(MAXL, p.Lk - k0);
@@ -114,7 +114,12 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
       m = mn;
     }
   }
-  if (live) {
+  if (live && p.mask_mode == 3 && l == 0.f) {  // fully masked row, mode 3: zero attention, finite lse (no key is read back)
+    float* op = O + (long long)n * p.bso + (long long)i * p.ldo + h * HD + sub * 8;
+    *reinterpret_cast<float4*>(op) = make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(op + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (sub == 0) lse[((long long)n * p.H + h) * p.Lq + i] = 0.f;
+  } else if (live) {
     const float inv = 1.f / l;                 // l == 0 (fully masked row) -> NaN like torch
     float* op = O + (long long)n * p.bso + (long long)i * p.ldo + h * HD + sub * 8;
     *reinterpret_cast<float4*>(op) = make_float4(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
@@ -142,7 +147,7 @@ __global__ void __launch_bounds__(64) attn_decode_kernel(const float* __restrict
     q[d] = a.x * p.scale; q[d + 1] = a.y * p.scale; q[d + 2] = a.z * p.scale; q[d + 3] = a.w * p.scale;
   }
   const int jmax = p.mask_mode == 1 ? min(p.Lk, p.causal_offset + 1) : p.Lk;
-  const uint8_t* kp = p.mask_mode == 2 ? p.kpm + (long long)n * p.Lk : nullptr;
+  const uint8_t* kp = p.mask_mode >= 2 ? p.kpm + (long long)n * p.Lk : nullptr;
   const float* kb = K + (long long)n * p.bsk + h * HD;
   float m = -INFINITY;
   for (int j = lane; j < jmax; j += 64) {
@@ -158,6 +163,11 @@ __global__ void __launch_bounds__(64) attn_decode_kernel(const float* __restrict
     m = fmaxf(m, s);
   }
   m = wave_max(m);
+  if (p.mask_mode == 3 && m == -INFINITY) {        // fully masked row, mode 3: zero attention (wave-uniform exit)
+    if (lane < 32) O[(long long)n * p.bso + h * HD + lane] = 0.f;
+    if (lane == 0) lse[(long long)n * p.H + h] = 0.f;
+    return;
+  }
   float l = 0.f;
   for (int j = lane; j < jmax; j += 64) {
     const float e = __expf(sc[j] - m);             // a fully masked row: m = -inf -> NaN like torch
@@ -218,7 +228,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const float* __restric
     const int last_row = min(p.Lq - 1, blockIdx.x * ROWS + ((threadIdx.x | 63) >> 2));
     jend = min(p.Lk, last_row + p.causal_offset + 1);
   }
-  const uint8_t* kp = p.mask_mode == 2 ? p.kpm + (long long)n * p.Lk : nullptr;
+  const uint8_t* kp = p.mask_mode >= 2 ? p.kpm + (long long)n * p.Lk : nullptr;
   const uint64_t rbase = (((uint64_t)n * p.H + h) * p.Lq + (uint64_t)(live ? i : 0)) * p.Lk;
   for (int kb = 0; kb < p.Lk; kb += MAXL) {
   const int kc = min(MAXL, p.Lk - kb);
@@ -281,7 +291,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const float* __restri
     const float* vp_ = V + (long long)n * p.bsv + (long long)j * p.ldv + h * HD + sub * 8;
 #pragma unroll
     for (int d = 0; d < 8; ++d) { k[d] = kp_[d] * p.scale; v[d] = vp_[d]; }
-    if (p.mask_mode == 2) keymasked = p.kpm[(long long)n * p.Lk + j] != 0;
+    if (p.mask_mode >= 2) keymasked = p.kpm[(long long)n * p.Lk + j] != 0;
   }
   uint64_t seed = 0, step = 0;
   if (p.thresh) { seed = p.rng_state[0]; step = p.rng_state[1]; }
@@ -371,7 +381,8 @@ __global__ void __launch_bounds__(256) attn_softmax_fwd_kernel(const float* __re
   const int i = (int)(row % p.Lq);
   const int n = (int)(row / ((long long)p.H * p.Lq));
   const float* s = S + row * p.Lk;
-  const uint8_t* kp = p.mask_mode == 2 ? p.kpm + (long long)n * p.Lk : nullptr;
+  const uint8_t* kp = p.mask_mode >= 2 ? p.kpm + (long long)n * p.Lk : nullptr;
+  const float dead = p.mask_mode == 3 ? 0.f : NAN;                          // a fully masked row: mode 3 gives zero attention
   const int jend = p.mask_mode == 1 ? min(p.Lk, i + p.causal_offset + 1) : p.Lk;
   uint64_t seed = 0, step = 0;
   if (p.thresh) { seed = p.rng_state[0]; step = p.rng_state[1]; }
@@ -396,7 +407,7 @@ __global__ void __launch_bounds__(256) attn_softmax_fwd_kernel(const float* __re
     for (int k = 0; k < 4; ++k) {
       const int j = lane + 64 * k;
       if (j < p.Lk) {
-        const float pv = live[k] ? v[k] * inv : (l == 0.f ? NAN : 0.f);
+        const float pv = live[k] ? v[k] * inv : (l == 0.f ? dead : 0.f);
         P[row * p.Lk + j] = pv;
         if (Pd) Pd[row * p.Lk + j] = cape_keep(seed, step, p.rng_stream, (uint64_t)row * p.Lk + j, p.thresh) ? pv * p.inv_keep : 0.f;
       }
@@ -414,7 +425,7 @@ __global__ void __launch_bounds__(256) attn_softmax_fwd_kernel(const float* __re
   const float inv = 1.f / l;
   for (int j = lane; j < p.Lk; j += 64) {
     const bool live = j < jend && !(kp && kp[j]);
-    const float pv = live ? __expf(s[j] * p.scale - m) * inv : (l == 0.f ? NAN : 0.f);
+    const float pv = live ? __expf(s[j] * p.scale - m) * inv : (l == 0.f ? dead : 0.f);
     P[row * p.Lk + j] = pv;
     if (Pd) Pd[row * p.Lk + j] = cape_keep(seed, step, p.rng_stream, (uint64_t)row * p.Lk + j, p.thresh) ? pv * p.inv_keep : 0.f;
   }
@@ -470,8 +481,8 @@ int fill(AttnP& p, long long ldq, long long ldk, long long ldv, long long ldo, c
   // forward and backward stage their panels MAXL rows at a time and take any length
   CAPE_REQUIRE(Lq >= 1 && Lk >= 1, "cape_attn: Lq=%d Lk=%d must be positive", Lq, Lk);
   CAPE_REQUIRE((ldq % 4) == 0 && (ldk % 4) == 0 && (ldv % 4) == 0 && (ldo % 4) == 0, "cape_attn: row strides must be multiples of 4");
-  CAPE_REQUIRE(mask_mode >= 0 && mask_mode <= 2, "cape_attn: bad mask_mode %d", mask_mode);
-  CAPE_REQUIRE(mask_mode != 2 || kpm, "cape_attn: key padding mask missing");
+  CAPE_REQUIRE(mask_mode >= 0 && mask_mode <= 3, "cape_attn: bad mask_mode %d", mask_mode);
+  CAPE_REQUIRE(mask_mode < 2 || kpm, "cape_attn: key padding mask missing");
   CAPE_REQUIRE(dropout_p == 0.f || (rng_state && dropout_p < 1.f), "cape_attn: dropout needs rng_state");
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
   p.bsq = bs[0]; p.bsk = bs[1]; p.bsv = bs[2]; p.bso = bs[3];

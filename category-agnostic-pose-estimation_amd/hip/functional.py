@@ -1451,6 +1451,108 @@ def zero_rows(x, rowmask_u8):
 
 
 # ------------------------------------------------------------------------------------------------
+# default (non-geometric) support encoder pieces (models/support_encoder.py)
+# ------------------------------------------------------------------------------------------------
+class LegacyCoordEmbedFn(torch.autograd.Function):
+    """coords (N,P,2) -> relu(Linear_2->C(coords)) (N,P,C); the coordinate gradient is produced when asked for."""
+
+    @staticmethod
+    def forward(ctx, coords, W0, b0):
+        coords = _c(coords)
+        N, P, _ = coords.shape
+        h = ops.legacy_coord_embed_fwd(coords, W0, b0)
+        ctx.save_for_backward(h, coords, W0)
+        ctx.refs = (W0, b0)
+        return h.view(N, P, -1)
+
+    @staticmethod
+    def backward(ctx, d_h):
+        h, coords, W0 = ctx.saved_tensors
+        pg = _ParamGrads(ctx.refs, ctx.needs_input_grad[1:3])
+        dW0, db0 = pg.bufs
+        if dW0 is None or db0 is None:                  # (the kernel takes both or neither)
+            dW0 = dW0 if dW0 is not None else torch.zeros_like(W0)
+            db0 = db0 if db0 is not None else torch.zeros(W0.shape[0], dtype=torch.float32, device=W0.device)
+        dc = ops.legacy_coord_embed_bwd(_c(d_h), h, coords, W0, dW0, db0, want_dcoords=ctx.needs_input_grad[0])
+        return (dc.view_as(coords) if dc is not None else None,) + pg.result()
+
+
+def legacy_coord_embed(coords, W0, b0):
+    return LegacyCoordEmbedFn.apply(coords, W0, b0)
+
+
+class EdgeCatFn(torch.autograd.Function):
+    """[h W2^T + b2 | edge_info] (N, P, 2C): the second coord_embedding linear writes the left half (GEMM with row stride 2C),
+    cape_support_edge_info_fwd the right half -- `torch.cat([coord_emb, edge_info])` of support_encoder.py:79 without a copy."""
+
+    @staticmethod
+    def forward(ctx, h, W2, b2, E, edges, start):
+        h = _c(h)
+        N, P, K = h.shape
+        C = W2.shape[0]
+        M = N * P
+        h2 = h.view(M, K)
+        cat = torch.empty(N, P, 2 * C, dtype=torch.float32, device=h.device)
+        cat2 = cat.view(M, 2 * C)
+        ops.gemm(h2, W2, cat2, M, C, K, ldb=W2.stride(0), bias=b2, ldc=2 * C)
+        scale, has, _ = ops.support_edge_info_fwd(edges, start, E, cat2[:, C:], N, P)
+        ctx.save_for_backward(h2, W2, scale, has)
+        ctx.refs = (W2, b2, E)
+        ctx.meta = (N, P, K, C)
+        return cat
+
+    @staticmethod
+    def backward(ctx, d_cat):
+        h2, W2, scale, has = ctx.saved_tensors
+        N, P, K, C = ctx.meta
+        M = N * P
+        g = _c(d_cat).view(M, 2 * C)
+        dh = None
+        if ctx.needs_input_grad[0]:
+            dh = torch.empty(M, K, dtype=torch.float32, device=g.device)
+            ops.gemm(g, W2, dh, M, K, C, a_mode=0, b_mode=1, lda=2 * C, ldb=W2.stride(0))
+            dh = dh.view(N, P, K)
+        pg = _ParamGrads(ctx.refs, ctx.needs_input_grad[1:4])
+        dW2, db2, dE = pg.bufs
+        if dE is not None:
+            ops.support_edge_info_bwd(g[:, C:], scale, has, dE)
+        with pg.side(g, h2):
+            if dW2 is not None:
+                pg.gemm(g, h2, dW2, C, K, M, a_mode=1, b_mode=1, lda=2 * C, ldb=K, ldc=dW2.stride(0), accumulate=True,
+                        split_k=ops.pick_split_k(C, K, M), colsum_out=db2)
+            elif db2 is not None:
+                ops.colsum(g, M, C, db2, ldx=2 * C)
+        return (dh,) + pg.result() + (None, None)
+
+
+def edge_cat(h, W2, b2, E, edges, start):
+    return EdgeCatFn.apply(h, W2, b2, E, edges, start)
+
+
+class PEDropoutFn(torch.autograd.Function):
+    """dropout(x + pe[:P]) -- PositionalEncoding1D.forward of support_encoder.py:151-159, in that order."""
+
+    @staticmethod
+    def forward(ctx, x, pe, dropout_p, rng_stream):
+        x = _c(x)
+        rng = Runtime.get_rng(x.device) if dropout_p > 0 else None
+        out = ops.pe_dropout_fwd(x, pe, x.shape[-2], dropout_p, rng, rng_stream)
+        ctx.meta = (dropout_p, rng_stream)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        p, stream = ctx.meta
+        if p == 0:
+            return g, None, None, None
+        return ops.pe_dropout_bwd(_c(g), p, Runtime.get_rng(g.device), stream), None, None, None
+
+
+def pe_dropout(x, pe, dropout_p=0.0, rng_stream=0):
+    return PEDropoutFn.apply(x, pe, float(dropout_p), int(rng_stream))
+
+
+# ------------------------------------------------------------------------------------------------
 # criterion
 # ------------------------------------------------------------------------------------------------
 class LossFn(torch.autograd.Function):

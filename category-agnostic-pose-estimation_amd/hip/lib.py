@@ -175,6 +175,12 @@ _SIGS = {
     "cape_gcn_aggregate_fwd": [P, P, P, I, I, I, P],
     "cape_gcn_aggregate_bwd": [P, P, P, P, I, I, I, P],
     "cape_zero_rows": [P, P, LL, I, P],
+    "cape_legacy_coord_embed_fwd": [P, P, P, P, I, I, P],
+    "cape_legacy_coord_embed_bwd": [P, P, P, P, P, P, P, I, I, P],
+    "cape_support_edge_info_fwd": [P, P, P, P, LL, P, P, P, I, I, I, P],
+    "cape_support_edge_info_bwd": [P, LL, P, P, P, I, I, P],
+    "cape_pe_dropout_fwd": [P, P, P, I, I, I, F, P, U32, P],
+    "cape_pe_dropout_bwd": [P, P, LL, F, P, U32, P],
     "cape_loss_fwd_bwd": [P, P, P, P, P, P, F, F, F, P, P, P, P, I, LL, P],
     "cape_sumsq": [P, LL, P, P],
     "cape_adamw_step": [P, P, P, P, LL, F, F, F, F, F, F, P, I, P, P, P],

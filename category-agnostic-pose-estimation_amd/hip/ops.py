@@ -1025,6 +1025,82 @@ def zero_rows(x, rowmask_u8):
     lib.call("cape_zero_rows", _p(x), _p(rowmask_u8), rows, C, _stream())
 
 
+# ------------------------------------------------------------------------------------------------
+# default (non-geometric) support encoder pieces (csrc/support_legacy.hip)
+# ------------------------------------------------------------------------------------------------
+def legacy_coord_embed_fwd(coords, W0, b0):
+    """h = relu(coords W0^T + b0): coords (..., 2) -> (R, C)."""
+    for t in (coords, W0, b0):
+        _chk(t, "legacy_coord_embed")
+    C = W0.shape[0]
+    R = coords.numel() // 2
+    assert W0.shape == (C, 2) and b0.numel() == C
+    h = torch.empty(R, C, dtype=_F32, device=coords.device)
+    lib.call("cape_legacy_coord_embed_fwd", _p(coords), _p(W0), _p(b0), _p(h), R, C, _stream())
+    return h
+
+
+def legacy_coord_embed_bwd(d_h, h, coords, W0, dW0=None, db0=None, want_dcoords=False):
+    """dW0 / db0 are accumulated into (both or neither); returns d_coords (R, 2) when asked for."""
+    for t in (d_h, h, coords, W0, dW0, db0):
+        _chk(t, "legacy_coord_embed_bwd")
+    R, C = h.shape
+    assert d_h.numel() == R * C and coords.numel() == 2 * R and (dW0 is None) == (db0 is None)
+    d_coords = torch.empty(R, 2, dtype=_F32, device=h.device) if want_dcoords else None
+    lib.call("cape_legacy_coord_embed_bwd", _p(d_h), _p(h), _p(coords), _p(W0), _p(dW0), _p(db0), _p(d_coords), R, C, _stream())
+    return d_coords
+
+
+def support_edge_info_fwd(edges_i32, edge_start_i32, E, out, N, P, want_degree=False):
+    """Writes edge_info (N*P, C) into `out` (a row-strided view, e.g. the right half of [coord_emb | edge_info]);
+    returns (scale (N*P,) float, has (N*P,) uint8, degree (N*P,) float or None)."""
+    _chk(edges_i32, "edge_info.edges", dtype=torch.int32)
+    _chk(edge_start_i32, "edge_info.start", dtype=torch.int32)
+    _chk(E, "edge_info.E")
+    _chk(out, "edge_info.out", contiguous=False)
+    C = E.shape[1]
+    assert E.shape == (2, C) and edge_start_i32.numel() == N + 1 and 1 <= P <= 256
+    assert out.dim() == 2 and out.shape == (N * P, C) and out.stride(1) == 1
+    assert _avail(out) >= (N * P - 1) * out.stride(0) + C
+    dev = E.device
+    scale = torch.empty(N * P, dtype=_F32, device=dev)
+    has = torch.empty(N * P, dtype=torch.uint8, device=dev)
+    deg = torch.empty(N * P, dtype=_F32, device=dev) if want_degree else None
+    lib.call("cape_support_edge_info_fwd", _p(edges_i32), _p(edge_start_i32), _p(E), _p(out), out.stride(0), _p(scale), _p(has),
+             _p(deg), N, P, C, _stream())
+    return scale, has, deg
+
+
+def support_edge_info_bwd(g, scale, has, dE):
+    """dE (2, C) += per-class sums of g * scale over the rows; g (R, C) may be row-strided."""
+    _chk(g, "edge_info_bwd.g", contiguous=False)
+    _chk(scale, "edge_info_bwd.scale"); _chk(has, "edge_info_bwd.has", dtype=torch.uint8); _chk(dE, "edge_info_bwd.dE")
+    R, C = g.shape
+    assert g.stride(1) == 1 and scale.numel() == R and has.numel() == R and dE.shape == (2, C)
+    assert _avail(g) >= (R - 1) * g.stride(0) + C
+    lib.call("cape_support_edge_info_bwd", _p(g), g.stride(0), _p(scale), _p(has), _p(dE), R, C, _stream())
+
+
+def pe_dropout_fwd(x, pe, P, dropout_p=0.0, rng=None, rng_stream=0, out=None):
+    """dropout(x + pe[row % P]) over x (R, C); `out` may be x (in place)."""
+    _chk(x, "pe_dropout.x"); _chk(pe, "pe_dropout.pe")
+    C = x.shape[-1]
+    R = x.numel() // C
+    assert pe.numel() >= P * C and R % P == 0
+    out = torch.empty_like(x) if out is None else out
+    _chk(out, "pe_dropout.out")
+    lib.call("cape_pe_dropout_fwd", _p(x), _p(pe), _p(out), R, P, C, float(dropout_p),
+             rng.ptr if (rng is not None and dropout_p > 0) else None, rng_stream, _stream())
+    return out
+
+
+def pe_dropout_bwd(g, dropout_p, rng, rng_stream):
+    _chk(g, "pe_dropout_bwd.g")
+    dx = torch.empty_like(g)
+    lib.call("cape_pe_dropout_bwd", _p(g), _p(dx), g.numel(), float(dropout_p), rng.ptr, rng_stream, _stream())
+    return dx
+
+
 def loss_fwd_bwd(logits, coords, labels, vis_u8, target, class_w, w_ce, w_l1, loss_scale):
     """logits (NL,R,3) coords (NL,R,2) -> losses (2*NL), total (1), d_logits, d_coords."""
     _chk(logits, "loss.logits"); _chk(coords, "loss.coords"); _chk(target, "loss.target"); _chk(class_w, "loss.cw")

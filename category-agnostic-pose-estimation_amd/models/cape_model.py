@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 
 from .geometric_support_encoder import GeometricSupportEncoder
+from .support_encoder import SupportPoseGraphEncoder
 
 
 class CAPEModel(nn.Module):
@@ -17,13 +18,14 @@ class CAPEModel(nn.Module):
         self.hidden_dim = hidden_dim
         self.support_fusion_method = support_fusion_method
         self.use_geometric_encoder = use_geometric_encoder
-        if not use_geometric_encoder:
-            raise ValueError("cape_amd implements the geometric support encoder (--use_geometric_encoder); the legacy "
-                             "SupportPoseGraphEncoder is outside the hot path named by the north star")
-        self.support_encoder = GeometricSupportEncoder(hidden_dim=hidden_dim, num_encoder_layers=support_encoder_layers,
-                                                       nhead=8, dim_feedforward=1024, dropout=0.1,
-                                                       use_gcn_preenc=use_gcn_preenc, num_gcn_layers=num_gcn_layers,
-                                                       activation="relu")
+        if use_geometric_encoder:
+            self.support_encoder = GeometricSupportEncoder(hidden_dim=hidden_dim, num_encoder_layers=support_encoder_layers,
+                                                           nhead=8, dim_feedforward=1024, dropout=0.1,
+                                                           use_gcn_preenc=use_gcn_preenc, num_gcn_layers=num_gcn_layers,
+                                                           activation="relu")
+        else:                                             # the reference's default (cape_model.py:44-51)
+            self.support_encoder = SupportPoseGraphEncoder(hidden_dim=hidden_dim, nheads=8, num_encoder_layers=support_encoder_layers,
+                                                           dim_feedforward=1024, dropout=0.1)
         if support_fusion_method == "cross_attention":
             self._add_support_cross_attention()
         elif support_fusion_method == "concat":
@@ -76,7 +78,8 @@ class CAPEModel(nn.Module):
         self._check(samples, support_coords, support_mask, skeleton_edges)
         if support_mask.dtype != torch.bool:
             support_mask = support_mask.bool()
-        encoder_mask = ~support_mask                      # the inversion of cape_model.py:120-124
+        # the inversion of cape_model.py:120-124 -- geometric encoder only; the default encoder inverts the mask itself
+        encoder_mask = ~support_mask if self.use_geometric_encoder else support_mask
         support_features = self.support_encoder(support_coords, encoder_mask, skeleton_edges)
         self._inject(support_features, support_mask)
         try:
@@ -91,7 +94,7 @@ class CAPEModel(nn.Module):
         events); the reference signature ends at `use_cache`."""
         if support_mask.dtype != torch.bool:
             support_mask = support_mask.bool()
-        encoder_mask = ~support_mask
+        encoder_mask = ~support_mask if self.use_geometric_encoder else support_mask
         support_features = self.support_encoder(support_coords, encoder_mask, skeleton_edges)
         self._inject(support_features, support_mask)
         try:

@@ -310,6 +310,9 @@ int cape_msda_bwd_atomic(const float* d_out, const float* value, const float* of
  *   O[n,i,h,:] = sum_j softmax_j(scale * Q[n,i,h,:].K[n,j,h,:] + mask) (dropped) V[n,j,h,:]
  * mask_mode 0 none, 1 causal (j <= i + causal_offset), 2 key padding (uint8 kpm[n][Lk], 1 = ignore).
  * lse (N,H,Lq) saved for backward.  Fully masked rows give NaN exactly like torch softmax(-inf row).
+ * mask_mode 3: key padding like 2, but a fully masked row gives O = 0 (lse 0) and no gradient -- torch's zero attention
+ * for such rows (SupportPoseGraphEncoder's inverted mask masks every key of a graph whose keypoints are all visible);
+ * also taken by cape_attn_softmax_fwd (P row = 0).
  * Replaces the core of nn.MultiheadAttention (deformable_transformer_v2.py:339, :352-355;
  * geometric_support_encoder.py:223-226).
  * ---------------------------------------------------------------------------------------------- */
@@ -468,6 +471,32 @@ int cape_gcn_aggregate_bwd(const float* d_out, const float* out, const float* ad
                            int P, int C, cape_stream_t stream);
 /* rows with rowmask[r] != 0 are set to zero (n floats per row) */
 int cape_zero_rows(float* x, const uint8_t* rowmask, long long rows, int C, cape_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Default (non-geometric) support encoder pieces (models/support_encoder.py of the reference; csrc/support_legacy.hip).
+ * Row reductions run in a fixed order (no float atomics).
+ * ---------------------------------------------------------------------------------------------- */
+/* h = relu(coords @ W0^T + b0): coords (R,2), W0 (C,2), h (R,C) */
+int cape_legacy_coord_embed_fwd(const float* coords, const float* W0, const float* b0, float* h, int R, int C, cape_stream_t stream);
+/* g = d_h o (h > 0): dW0 (+)= g^T coords, db0 (+)= colsum g (both or neither); d_coords = g W0 (optional, written) */
+int cape_legacy_coord_embed_bwd(const float* d_h, const float* h, const float* coords, const float* W0, float* dW0, float* db0,
+                                float* d_coords, int R, int C, cape_stream_t stream);
+/* _build_adjacency_matrix + _aggregate_edge_embeddings (support_encoder.py:94-133), one block per graph: edge (s, d) of the flat
+ * int32 list (edge_start (N+1) offsets) -> index s-1 if s > 0 else s, kept if in [0, P), set symmetrically (duplicates once);
+ * deg = row sum.  out[r][c] (row stride ldo, e.g. the right half of [coord_emb | edge_info]) = E[deg > 0][c] * max(deg, 1) / 10,
+ * E = edge_embedding.weight (2, C); scale[r] = max(deg, 1) / 10, has[r] = deg > 0 (saved for the backward); deg (optional) = deg.
+ * P <= 256. */
+int cape_support_edge_info_fwd(const int* edges, const int* edge_start, const float* E, float* out, long long ldo, float* scale,
+                               uint8_t* has, float* deg, int N, int P, int C, cape_stream_t stream);
+/* dE[k][c] (+)= sum_{r: has[r] == k} g[r][c] * scale[r]  (g row stride ldg) */
+int cape_support_edge_info_bwd(const float* g, long long ldg, const float* scale, const uint8_t* has, float* dE, int R, int C,
+                               cape_stream_t stream);
+/* PositionalEncoding1D.forward (support_encoder.py:151-159): out = dropout(x + pe[r % P]) over (R, C), out may be x; the
+ * dropout element index is r*C + c on stream `rng_stream`.  bwd (0 < p < 1): dx = keep ? g / (1-p) : 0. */
+int cape_pe_dropout_fwd(const float* x, const float* pe, float* out, int R, int P, int C, float dropout_p, const uint64_t* rng_state,
+                        uint32_t rng_stream, cape_stream_t stream);
+int cape_pe_dropout_bwd(const float* g, float* dx, long long total, float dropout_p, const uint64_t* rng_state, uint32_t rng_stream,
+                        cape_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Loss (models/cape_losses.py:71-163, roomformer_v2.py:915-953), all NL decoder layers at once.
