@@ -136,7 +136,7 @@ def test_cached_decode_vs_reference_golden(golden_dir, proc_sd, name):
         pe = model.forward_inference(samples=b["images"], support_coords=b["support_coords"],
                                      support_mask=b["support_mask"], skeleton_edges=b["skeleton"], graph=False)
         assert torch.equal(pe["logits"], p["logits"])
-    assert len(model.base_model._decode_states) == 1 and len(next(iter(model.base_model._decode_states.values()))["graphs"]) >= p["logits"].shape[1]
+    assert len(model.base_model._decode_states) == 1 and len(next(iter(model.base_model._decode_states.values())).graphs) >= p["logits"].shape[1]
     top2 = ref_logits.sort(-1).values
     clear = (top2[..., 2] - top2[..., 1]) > 5e-2
     assert torch.equal(p["sequences"].cpu()[clear], t(d["sequences"]).long()[clear])
