@@ -851,24 +851,26 @@ class BiAttnCoreFn(torch.autograd.Function):
         rv_l, rv_p = _c(rv_l), _c(rv_p)
         B, Nl, D2 = rv_l.shape
         Np, D = rv_p.shape[1], D2 // 2
-        lat, lse1 = ops.attn_fwd(rv_l[..., :D], rv_p[..., :D], rv_p[..., D:], B, nheads, Nl, Np, scale)
-        pat, lse2 = ops.attn_fwd(rv_p[..., :D], rv_l[..., :D], rv_l[..., D:], B, nheads, Np, Nl, scale)
-        ctx.save_for_backward(rv_l, rv_p, lat, pat, lse1, lse2)
+        ctx.route = "scalar"
+        lat, s1 = ops.attn_core_fwd(ctx.route, rv_l[..., :D], rv_p[..., :D], rv_p[..., D:], B, nheads, Nl, Np, scale)
+        pat, s2 = ops.attn_core_fwd(ctx.route, rv_p[..., :D], rv_l[..., :D], rv_l[..., D:], B, nheads, Np, Nl, scale)
+        ctx.save_for_backward(rv_l, rv_p, lat, pat, *s1, *s2)
         ctx.meta = (nheads, scale)
         return lat, pat
 
     @staticmethod
     def backward(ctx, d_lat, d_pat):
-        rv_l, rv_p, lat, pat, lse1, lse2 = ctx.saved_tensors
+        rv_l, rv_p, lat, pat, *saved = ctx.saved_tensors
+        s1, s2 = saved[:len(saved) // 2], saved[len(saved) // 2:]
         nheads, scale = ctx.meta
         B, Nl, D2 = rv_l.shape
         Np, D = rv_p.shape[1], D2 // 2
         d_l, d_p = torch.empty_like(rv_l), torch.empty_like(rv_p)
         t_l, t_p = torch.empty_like(rv_l), torch.empty_like(rv_p)     # (only the r halves are used: same row stride as the inputs)
-        ops.attn_bwd(_c(d_lat), rv_l[..., :D], rv_p[..., :D], rv_p[..., D:], lat, lse1, d_l[..., :D], d_p[..., :D], d_p[..., D:],
-                     B, nheads, Nl, Np, scale)
-        ops.attn_bwd(_c(d_pat), rv_p[..., :D], rv_l[..., :D], rv_l[..., D:], pat, lse2, t_p[..., :D], t_l[..., :D], d_l[..., D:],
-                     B, nheads, Np, Nl, scale)
+        ops.attn_core_bwd(ctx.route, s1, _c(d_lat), rv_l[..., :D], rv_p[..., :D], rv_p[..., D:], lat, d_l[..., :D], d_p[..., :D],
+                          d_p[..., D:], B, nheads, Nl, Np, scale)
+        ops.attn_core_bwd(ctx.route, s2, _c(d_pat), rv_p[..., :D], rv_l[..., :D], rv_l[..., D:], pat, t_p[..., :D], t_l[..., :D],
+                          d_l[..., D:], B, nheads, Np, Nl, scale)
         ops.add_n_rows([d_l[..., :D], t_l[..., :D]], out=d_l[..., :D])
         ops.add_n_rows([d_p[..., :D], t_p[..., :D]], out=d_p[..., :D])
         return d_l, d_p, None, None
@@ -886,19 +888,21 @@ class AttnKVFn(torch.autograd.Function):
         r_q, rv_kv = _c(r_q), _c(rv_kv)
         B, Nq, D = r_q.shape
         Nk = rv_kv.shape[1]
-        out, lse = ops.attn_fwd(r_q, rv_kv[..., :D], rv_kv[..., D:], B, nheads, Nq, Nk, scale)
-        ctx.save_for_backward(r_q, rv_kv, out, lse)
+        ctx.route = "scalar"
+        out, saved = ops.attn_core_fwd(ctx.route, r_q, rv_kv[..., :D], rv_kv[..., D:], B, nheads, Nq, Nk, scale)
+        ctx.save_for_backward(r_q, rv_kv, out, *saved)
         ctx.meta = (nheads, scale)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        r_q, rv_kv, out, lse = ctx.saved_tensors
+        r_q, rv_kv, out, *saved = ctx.saved_tensors
         nheads, scale = ctx.meta
         B, Nq, D = r_q.shape
         Nk = rv_kv.shape[1]
         dq, dkv = torch.empty_like(r_q), torch.empty_like(rv_kv)
-        ops.attn_bwd(_c(d_out), r_q, rv_kv[..., :D], rv_kv[..., D:], out, lse, dq, dkv[..., :D], dkv[..., D:], B, nheads, Nq, Nk, scale)
+        ops.attn_core_bwd(ctx.route, saved, _c(d_out), r_q, rv_kv[..., :D], rv_kv[..., D:], out, dq, dkv[..., :D], dkv[..., D:], B, nheads,
+                          Nq, Nk, scale)
         return dq, dkv, None, None
 
 
@@ -1030,63 +1034,61 @@ def msda(value, offw, ref, geo, P=4):
 # ------------------------------------------------------------------------------------------------
 # nn.MultiheadAttention (in_proj + core + out_proj) as one node
 # ------------------------------------------------------------------------------------------------
+def _from_row(t, r):
+    return t if (t is None or r == 0) else t[r:]
+
+
+def _col_blocks(groups, bufs, C):
+    """The q, k, v column blocks of the groups' buffers (see MHAFn)."""
+    return [buf[..., j * C:(j + 1) * C] for (_, w, *_), buf in zip(groups, bufs) for j in range(w)]
+
+
 class MHAFn(torch.autograd.Function):
+    """The in-projection runs as a list of GROUPS (r, w, dup): w consecutive C-row blocks of in_proj_weight from block r on, applied
+    to the r-th input (q_in, k_in, v_in = inputs 0, 1, 2) in ONE product whose result buffer (N, L, wC) holds the w projections
+    as column blocks.  A group costs one product forward and two backward (weight and data gradient).  Projections of the same
+    input share a group (the support encoder's self-attention, q = k = v: one group, N = 768; cross-attention onto the support
+    features, k = v: two groups, N = 256 and 512) unless the attention route is "mm"; the scalar attention kernels take the
+    column views (row stride 3C / 2C) as they are.  dup: the input is the tensor that also came in as k."""
+
     @staticmethod
     def forward(ctx, q_in, k_in, v_in, in_w, in_b, out_w, out_b, nheads, mask_mode, kpm_u8, dropout_p, rng_stream):
-        q_in, k_in, v_in = _c(q_in), _c(k_in), _c(v_in)
+        ins = q_in, k_in, v_in = _c(q_in), _c(k_in), _c(v_in)
         N, Lq, C = q_in.shape
         Lk = k_in.shape[1]
         dev = q_in.device
         scale = (C // nheads) ** -0.5
         rng = Runtime.get_rng(dev) if dropout_p > 0 else None
-        mm = ops.attn_mm_ok(N, nheads, Lq, Lk)      # long rows: contractions on the matrix cores, softmax kernel in between
-        # projections of the same input are ONE launch over the stacked in_proj rows (the support encoder's self-attention:
-        # q = k = v -> N = 768; cross-attention onto the support features: k = v -> N = 512); q / k / v are then column views of
-        # the wide result (row stride 3C / 2C), which the short-row attention kernels take as they are
-        merged = 0
-        if not mm and k_in is v_in:
-            merged = 3 if (q_in is k_in) else 2
-        if merged == 3:
-            qkv = torch.empty(N, Lq, 3 * C, dtype=torch.float32, device=dev)
-            ops.gemm(q_in.view(-1, C), in_w, qkv, N * Lq, 3 * C, C, bias=in_b)
-            q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+        ctx.route = ops.attn_route(N, nheads, Lq, Lk, flash=False)
+        if ctx.route != "mm" and k_in is v_in:
+            layout = ((0, 3),) if q_in is k_in else ((0, 1), (1, 2))
         else:
-            q = torch.empty(N, Lq, C, dtype=torch.float32, device=dev)
-            ops.gemm(q_in.view(-1, C), in_w, q, N * Lq, C, C, bias=in_b)
-            if merged == 2:
-                kv = torch.empty(N, Lk, 2 * C, dtype=torch.float32, device=dev)
-                ops.gemm(k_in.view(-1, C), in_w[C:], kv, N * Lk, 2 * C, C, bias=in_b[C:])
-                k, v = kv[..., :C], kv[..., C:]
-            else:
-                k = torch.empty(N, Lk, C, dtype=torch.float32, device=dev)
-                v = torch.empty(N, Lk, C, dtype=torch.float32, device=dev)
-                ops.gemm(k_in.view(-1, C), in_w[C:], k, N * Lk, C, C, bias=in_b[C:])
-                ops.gemm(v_in.view(-1, C), in_w[2 * C:], v, N * Lk, C, C, bias=in_b[2 * C:])
-        if mm:
-            O, Pp, Pu = ops.attn_mm_fwd(q, k, v, N, nheads, Lq, Lk, scale, mask_mode=mask_mode, kpm=kpm_u8, dropout_p=dropout_p,
-                                        rng=rng, rng_stream=rng_stream)
-            lse = Pp
-            ctx.Pu = Pu
-        else:
-            O, lse = ops.attn_fwd(q, k, v, N, nheads, Lq, Lk, scale, mask_mode=mask_mode, kpm=kpm_u8, dropout_p=dropout_p,
-                                  rng=rng, rng_stream=rng_stream)
+            layout = ((0, 1), (1, 1), (2, 1))
+        ctx.groups = tuple((r, w, r != 1 and ins[r] is k_in) for r, w in layout)
+        bufs = [torch.empty(N, ins[r].shape[1], w * C, dtype=torch.float32, device=dev) for r, w in layout]
+        for (r, w), buf in zip(layout, bufs):
+            ops.gemm(ins[r].view(-1, C), _from_row(in_w, r * C), buf, N * ins[r].shape[1], w * C, C, bias=_from_row(in_b, r * C))
+        q, k, v = _col_blocks(layout, bufs, C)
+        O, saved = ops.attn_core_fwd(ctx.route, q, k, v, N, nheads, Lq, Lk, scale, mask_mode=mask_mode, kpm=kpm_u8, dropout_p=dropout_p,
+                                     rng=rng, rng_stream=rng_stream)
         out = torch.empty(N, Lq, C, dtype=torch.float32, device=dev)
         ops.gemm(O.view(-1, C), out_w, out, N * Lq, C, C, bias=out_b)
-        ctx.save_for_backward(q_in, k_in, v_in, in_w, out_w, q, k, v, O, lse, kpm_u8)
+        ctx.save_for_backward(q_in, k_in, v_in, in_w, out_w, q, k, v, O, kpm_u8, *saved)
         ctx.refs = (in_w, in_b, out_w, out_b)
         ctx.slot_q = _slot_of(q_in)
-        ctx.meta = (nheads, mask_mode, dropout_p, rng_stream, scale, k_in is v_in, q_in is k_in, mm, merged)
+        ctx.meta = (nheads, mask_mode, dropout_p, rng_stream, scale)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        q_in, k_in, v_in, in_w, out_w, q, k, v, O, lse, kpm = ctx.saved_tensors
-        nheads, mask_mode, p, stream, scale, kv_same, qk_same, mm, merged = ctx.meta
+        q_in, k_in, v_in, in_w, out_w, q, k, v, O, kpm, *saved = ctx.saved_tensors
+        nheads, mask_mode, p, stream, scale = ctx.meta
+        ins = q_in, k_in, v_in
         N, Lq, C = q_in.shape
         Lk = k_in.shape[1]
         dev = d_out.device
         d_out2 = _c(d_out).view(-1, C)
-        Mq, Mk = N * Lq, N * Lk
+        Mq = N * Lq
         dO = torch.empty(Mq, C, dtype=torch.float32, device=dev)
         ops.gemm(d_out2, out_w, dO, Mq, C, C, a_mode=0, b_mode=1)
         pg = _ParamGrads(ctx.refs)
@@ -1094,74 +1096,39 @@ class MHAFn(torch.autograd.Function):
         with pg.side(d_out2, O):
             pg.gemm(d_out2, O.view(-1, C), d_out_w, C, C, Mq, a_mode=1, b_mode=1, accumulate=True,
                     split_k=ops.pick_split_k(C, C, Mq), colsum_out=d_out_b)
-        if merged == 3:                              # gradients in the layout of the wide projection result
-            dqkv = torch.empty(N, Lq, 3 * C, dtype=torch.float32, device=dev)
-            dq, dk, dv = dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]
-        elif merged == 2:
-            dq = torch.empty(N, Lq, C, dtype=torch.float32, device=dev)
-            dkv = torch.empty(N, Lk, 2 * C, dtype=torch.float32, device=dev)
-            dk, dv = dkv[..., :C], dkv[..., C:]
-        else:
-            dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        # gradients in the layout of the projection results: one buffer per group, dq / dk / dv its column blocks
+        dbufs = [torch.empty(N, ins[r].shape[1], w * C, dtype=torch.float32, device=dev) for r, w, _ in ctx.groups]
+        dq, dk, dv = _col_blocks(ctx.groups, dbufs, C)
         rng = Runtime.get_rng(dev) if p > 0 else None
-        if mm:
-            ops.attn_mm_bwd(dO.view(N, Lq, C), q, k, v, lse, ctx.Pu, dq, dk, dv, N, nheads, Lq, Lk, scale, dropout_p=p, rng=rng,
-                            rng_stream=stream)
-        else:
-            ops.attn_bwd(dO.view(N, Lq, C), q, k, v, O, lse, dq, dk, dv, N, nheads, Lq, Lk, scale, mask_mode=mask_mode, kpm=kpm,
-                         dropout_p=p, rng=rng, rng_stream=stream)
-
-        with pg.side(dq, dk, dv, q_in, k_in, v_in):
-            if merged == 3:                          # [dq | dk | dv]^T x: one product for the stacked in_proj rows
-                pg.gemm(dqkv.view(-1, 3 * C), q_in.view(-1, C), d_in_w, 3 * C, C, Mq, a_mode=1, b_mode=1, lda=3 * C, accumulate=True,
-                        split_k=ops.pick_split_k(3 * C, C, Mq), colsum_out=d_in_b)
-            else:
-                pg.gemm(dq.view(-1, C), q_in.view(-1, C), d_in_w, C, C, Mq, a_mode=1, b_mode=1, accumulate=True,
-                        split_k=ops.pick_split_k(C, C, Mq), colsum_out=d_in_b)
-            if merged == 2:
-                pg.gemm(dkv.view(-1, 2 * C), k_in.view(-1, C), d_in_w[C:], 2 * C, C, Mk, a_mode=1, b_mode=1, lda=2 * C, accumulate=True,
-                        split_k=ops.pick_split_k(2 * C, C, Mk), colsum_out=d_in_b[C:])
-            elif merged == 0:
-                for i, g, src in ((1, dk, k_in), (2, dv, v_in)):
-                    pg.gemm(g.view(-1, C), src.view(-1, C), d_in_w[i * C:], C, C, Mk, a_mode=1, b_mode=1, accumulate=True,
-                            split_k=ops.pick_split_k(C, C, Mk), colsum_out=d_in_b[i * C:])
+        ops.attn_core_bwd(ctx.route, saved, dO.view(N, Lq, C), q, k, v, O, dq, dk, dv, N, nheads, Lq, Lk, scale, mask_mode=mask_mode,
+                          kpm=kpm, dropout_p=p, rng=rng, rng_stream=stream)
+        pairs = list(zip(ctx.groups, dbufs))
+        with pg.side(*dbufs, q_in, k_in, v_in):
+            for (r, w, _), g in pairs:                       # [d heads of the group]^T x: one product for its stacked in_proj rows
+                M = N * ins[r].shape[1]
+                pg.gemm(g.view(-1, w * C), ins[r].view(-1, C), _from_row(d_in_w, r * C), w * C, C, M, a_mode=1, b_mode=1, lda=w * C,
+                        accumulate=True, split_k=ops.pick_split_k(w * C, C, M), colsum_out=_from_row(d_in_b, r * C))
         d_in_w, d_in_b, d_out_w, d_out_b = pg.result()
-        # input gradients; when the same tensor came in as k and v (support features) or as q, k and v (self-attention of the
-        # support encoder) the products accumulate into ONE buffer (GEMM epilogue C += ...) and the duplicates report None
-        dq_in = dk_in = dv_in = None
-        need_q, need_k, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if merged == 3 and (need_q or need_k or need_v):
-            # d x = [dq | dk | dv] . in_proj_weight: one product with K = 3C; the one tensor reports through its first live slot
-            dx = torch.empty(N, Lq, C, dtype=torch.float32, device=dev)
-            ops.gemm(dqkv.view(-1, 3 * C), in_w, dx, Mq, C, 3 * C, a_mode=0, b_mode=1)
-            return ((dx if need_q else None), (dx if (need_k and not need_q) else None), (dx if (need_v and not (need_q or need_k)) else None),
-                    d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None, None)
-        if merged == 2:
-            if need_k or need_v:
-                dk_in = torch.empty(N, Lk, C, dtype=torch.float32, device=dev)
-                ops.gemm(dkv.view(-1, 2 * C), in_w[C:], dk_in, Mk, C, 2 * C, a_mode=0, b_mode=1)
-                if not need_k:
-                    dv_in, dk_in = dk_in, None
-            if need_q:
-                dq_in, acc = _grad_target(ctx.slot_q, (N, Lq, C), dev)
-                ops.gemm(dq.view(-1, C), in_w, dq_in, Mq, C, C, a_mode=0, b_mode=1, accumulate=acc)
-            return dq_in, dk_in, dv_in, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None, None
-        if need_k:
-            dk_in = torch.empty(N, Lk, C, dtype=torch.float32, device=dev)
-            ops.gemm(dk.view(-1, C), in_w[C:], dk_in, Mk, C, C, a_mode=0, b_mode=1)
-        if need_v:
-            if kv_same and dk_in is not None:
-                ops.gemm(dv.view(-1, C), in_w[2 * C:], dk_in, Mk, C, C, a_mode=0, b_mode=1, accumulate=True)
+        # input gradients, d x = [d heads of the group] . its in_proj rows (K = wC), the key side first: the product of a tensor
+        # that also came in as k adds into d k_in (GEMM epilogue C += ...) and reports None; any other gradient reports through
+        # the first slot of its group that needs one
+        d_ins, dk_in = [None, None, None], None
+        for (r, w, dup), g in pairs[1:] + pairs[:1]:
+            live = [j for j in range(r, r + w) if ctx.needs_input_grad[j]]
+            if not live:
+                continue
+            if dup and dk_in is not None:
+                dst, acc = dk_in, True
             else:
-                dv_in = torch.empty(N, Lk, C, dtype=torch.float32, device=dev)
-                ops.gemm(dv.view(-1, C), in_w[2 * C:], dv_in, Mk, C, C, a_mode=0, b_mode=1)
-        if need_q:
-            if qk_same and dk_in is not None:
-                ops.gemm(dq.view(-1, C), in_w, dk_in, Mq, C, C, a_mode=0, b_mode=1, accumulate=True)
-            else:
-                dq_in = torch.empty(N, Lq, C, dtype=torch.float32, device=dev)
-                ops.gemm(dq.view(-1, C), in_w, dq_in, Mq, C, C, a_mode=0, b_mode=1)
-        return dq_in, dk_in, dv_in, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None, None
+                if r == 0 and len(pairs) == 2:               # (the query of cross-attention onto k = v: a fan-out consumer)
+                    dst, acc = _grad_target(ctx.slot_q, ins[r].shape, dev)
+                else:
+                    dst, acc = torch.empty(ins[r].shape, dtype=torch.float32, device=dev), False
+                d_ins[live[0]] = dst
+            ops.gemm(g.view(-1, w * C), _from_row(in_w, r * C), dst, N * ins[r].shape[1], C, w * C, a_mode=0, b_mode=1, accumulate=acc)
+            if live[0] == 1:
+                dk_in = dst
+        return (*d_ins, d_in_w, d_in_b, d_out_w, d_out_b, None, None, None, None, None)
 
 
 class DecSelfAttnFn(torch.autograd.Function):
@@ -1194,29 +1161,21 @@ class DecSelfAttnFn(torch.autograd.Function):
         q, k, v = qkv2[..., :C], qkv2[..., C:2 * C], qkv2[..., 2 * C:]
         scale = (C // nheads) ** -0.5
         rng = Runtime.get_rng(dev) if dropout_p > 0 else None
-        flash = ops.flash_attn_ok(N, nheads, L, L)
-        mm = (not flash) and ops.attn_mm_ok(N, nheads, L, L)
-        if flash:
-            O, lse = ops.flash_attn_fwd(q, k, v, N, nheads, L, L, scale, mask_mode=1, dropout_p=dropout_p, rng=rng, rng_stream=rng_stream)
-        elif mm:
-            O, Pp, Pu = ops.attn_mm_fwd(q, k, v, N, nheads, L, L, scale, mask_mode=1, dropout_p=dropout_p, rng=rng, rng_stream=rng_stream)
-            lse = Pp
-            ctx.Pu = Pu
-        else:
-            O, lse = ops.attn_fwd(q, k, v, N, nheads, L, L, scale, mask_mode=1, dropout_p=dropout_p, rng=rng, rng_stream=rng_stream)
+        ctx.route = ops.attn_route(N, nheads, L, L, flash=True)
+        O, saved = ops.attn_core_fwd(ctx.route, q, k, v, N, nheads, L, L, scale, mask_mode=1, dropout_p=dropout_p, rng=rng,
+                                     rng_stream=rng_stream)
         out = torch.empty(N, L, C, dtype=torch.float32, device=dev)
         ops.gemm(O.view(M, C), out_w, out, M, C, C, bias=out_b)
-        ctx.save_for_backward(x, wq, wk, wv, in_w, out_w, qkv1, qkv2, O, lse)
+        ctx.save_for_backward(x, wq, wk, wv, in_w, out_w, qkv1, qkv2, O, *saved)
         ctx.refs = (wq, wk, wv, in_w, in_b, out_w, out_b)
-        ctx.meta = (nheads, dropout_p, rng_stream, scale, mm, stacked, N, L, C)
-        ctx.flash = flash
+        ctx.meta = (nheads, dropout_p, rng_stream, scale, stacked, N, L, C)
         ctx.slot = _slot_of(tgt)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        x, wq, wk, wv, in_w, out_w, qkv1, qkv2, O, lse = ctx.saved_tensors
-        nheads, p, stream, scale, mm, stacked, N, L, C = ctx.meta
+        x, wq, wk, wv, in_w, out_w, qkv1, qkv2, O, *saved = ctx.saved_tensors
+        nheads, p, stream, scale, stacked, N, L, C = ctx.meta
         M = N * L
         dev = d_out.device
         d_out2 = _c(d_out).view(M, C)
@@ -1226,14 +1185,8 @@ class DecSelfAttnFn(torch.autograd.Function):
         dq, dk, dv = dqkv2[..., :C], dqkv2[..., C:2 * C], dqkv2[..., 2 * C:]
         q, k, v = qkv2[..., :C], qkv2[..., C:2 * C], qkv2[..., 2 * C:]
         rng = Runtime.get_rng(dev) if p > 0 else None
-        if ctx.flash:
-            ops.flash_attn_bwd(dO.view(N, L, C), q, k, v, O, lse, dq, dk, dv, N, nheads, L, L, scale, mask_mode=1, dropout_p=p, rng=rng,
-                               rng_stream=stream)
-        elif mm:
-            ops.attn_mm_bwd(dO.view(N, L, C), q, k, v, lse, ctx.Pu, dq, dk, dv, N, nheads, L, L, scale, dropout_p=p, rng=rng, rng_stream=stream)
-        else:
-            ops.attn_bwd(dO.view(N, L, C), q, k, v, O, lse, dq, dk, dv, N, nheads, L, L, scale, mask_mode=1, dropout_p=p, rng=rng,
-                         rng_stream=stream)
+        ops.attn_core_bwd(ctx.route, saved, dO.view(N, L, C), q, k, v, O, dq, dk, dv, N, nheads, L, L, scale, mask_mode=1, dropout_p=p,
+                          rng=rng, rng_stream=stream)
         dqkv1 = torch.empty(M, 3 * C, dtype=torch.float32, device=dev)
         ops.gemm(dqkv2.view(M, 3 * C), in_w, dqkv1, M, C, C, a_mode=0, b_mode=1, lda=3 * C, ldb=C, ldc=3 * C,
                  batch=(3, 3, 0, C, 0, C * C, 0, C))

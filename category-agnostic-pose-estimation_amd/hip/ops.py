@@ -541,22 +541,67 @@ def _ld(t):
     return t.stride(-2)
 
 
-def attn_fwd(Q, K, V, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=None, dropout_p=0.0, rng=None, rng_stream=0):
-    """Q (N,Lq,*) K,V (N,Lk,*) as (possibly strided) views whose last dim holds H*32 head channels."""
+def _attn_views(tag, Q, K, V, N, H, Lq, Lk, flash):
+    """Operand checks of the scalar and the fused kernels: (N, L, H*32) views inside their storage; the fused kernels also want
+    dense head channels, 16-byte aligned rows and images."""
     for t, n, L_ in ((Q, "Q", Lq), (K, "K", Lk), (V, "V", Lk)):
-        _chk(t, "attn." + n, contiguous=False)
+        _chk(t, tag + "." + n, contiguous=False)
         assert t.dim() == 3 and t.shape[0] == N and t.shape[1] >= L_ and t.shape[2] == H * 32
+        if flash:
+            assert t.stride(2) == 1 and t.stride(1) % 4 == 0 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
         assert _avail(t) >= (N - 1) * t.stride(0) + (L_ - 1) * t.stride(1) + H * 32
+
+
+def _rng_ptr(rng, dropout_p):
+    return rng.ptr if (rng is not None and dropout_p > 0) else None
+
+
+def _attn_tail(Q, K, V, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream):
+    """The arguments every cape_attn_* / cape_flash_attn_* entry point takes after its tensor pointers."""
+    return (_ld(Q), _ld(K), _ld(V), H * 32, Q.stride(0), K.stride(0), V.stride(0), Lq * H * 32, N, H, Lq, Lk, float(scale), mask_mode,
+            causal_offset, _p(kpm), float(dropout_p), _rng_ptr(rng, dropout_p), rng_stream, _stream())
+
+
+def _attn_fwd(flash, Q, K, V, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream):
+    tag = "flash_attn" if flash else "attn"
+    _attn_views(tag, Q, K, V, N, H, Lq, Lk, flash)
     if kpm is not None:
-        _chk(kpm, "attn.kpm", dtype=torch.uint8)
+        _chk(kpm, tag + ".kpm", dtype=torch.uint8)
         assert kpm.numel() == N * Lk
     O = torch.empty(N, Lq, H * 32, dtype=_F32, device=Q.device)
     lse = torch.empty(N, H, Lq, dtype=_F32, device=Q.device)
-    lib.call("cape_attn_fwd", _p(Q), _p(K), _p(V), _p(O), _p(lse), _ld(Q), _ld(K), _ld(V), H * 32,
-             Q.stride(0), K.stride(0), V.stride(0), Lq * H * 32, N, H, Lq, Lk,
-             float(scale), mask_mode, causal_offset, _p(kpm), float(dropout_p),
-             rng.ptr if (rng is not None and dropout_p > 0) else None, rng_stream, _stream())
+    lib.call("cape_" + tag + "_fwd", _p(Q), _p(K), _p(V), _p(O), _p(lse),
+             *_attn_tail(Q, K, V, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream))
     return O, lse
+
+
+def _attn_bwd(flash, dO, Q, K, V, O, lse, dQ, dK, dV, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream):
+    tag = "flash_attn_bwd" if flash else "attn_bwd"
+    _chk(dO, tag + ".dO")
+    for t in (dQ, dK, dV):
+        _chk(t, tag + ".grad", contiguous=False)
+    assert _ld(dQ) == _ld(Q) and _ld(dK) == _ld(K) and _ld(dV) == _ld(V)
+    assert dQ.stride(0) == Q.stride(0) and dK.stride(0) == K.stride(0) and dV.stride(0) == V.stride(0)
+    assert O.is_contiguous() and dO.shape == O.shape
+    ws = None
+    if flash:
+        _attn_views("flash_attn", Q, K, V, N, H, Lq, Lk, True)
+        _attn_views("flash_attn", dQ, dK, dV, N, H, Lq, Lk, True)
+        _chk(O, tag + ".O"); _chk(lse, tag + ".lse")
+        assert O.shape == (N, Lq, H * 32) and lse.numel() == N * H * Lq
+        ws = torch.empty(N * H * Lq, dtype=_F32, device=dO.device)          # the fused kernel's row sums of dO * O
+    lib.call("cape_" + tag, _p(dO), _p(Q), _p(K), _p(V), _p(O), _p(lse), _p(dQ), _p(dK), _p(dV), *((_p(ws),) if flash else ()),
+             *_attn_tail(Q, K, V, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream))
+
+
+def attn_fwd(Q, K, V, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=None, dropout_p=0.0, rng=None, rng_stream=0):
+    """Q (N,Lq,*) K,V (N,Lk,*) as (possibly strided) views whose last dim holds H*32 head channels."""
+    return _attn_fwd(False, Q, K, V, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream)
+
+
+def attn_bwd(dO, Q, K, V, O, lse, dQ, dK, dV, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=None, dropout_p=0.0,
+             rng=None, rng_stream=0):
+    _attn_bwd(False, dO, Q, K, V, O, lse, dQ, dK, dV, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream)
 
 
 FLASH_MAX_L = 224
@@ -568,40 +613,14 @@ def flash_attn_ok(N, H, Lq, Lk):
             and N <= 65535 and H <= 65535)
 
 
-def _flash_views(Q, K, V, N, H, Lq, Lk):
-    for t, n, L_ in ((Q, "Q", Lq), (K, "K", Lk), (V, "V", Lk)):
-        _chk(t, "flash_attn." + n, contiguous=False)
-        assert t.dim() == 3 and t.shape[0] == N and t.shape[1] >= L_ and t.shape[2] == H * 32 and t.stride(2) == 1
-        assert t.stride(1) % 4 == 0 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
-        assert _avail(t) >= (N - 1) * t.stride(0) + (L_ - 1) * t.stride(1) + H * 32
-
-
 def flash_attn_fwd(Q, K, V, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=None, dropout_p=0.0, rng=None, rng_stream=0):
     """Q (N, Lq, H*32) / K, V (N, Lk, H*32) possibly strided views -> O (N, Lq, H*32) contiguous, lse (N, H, Lq)."""
-    _flash_views(Q, K, V, N, H, Lq, Lk)
-    if kpm is not None:
-        _chk(kpm, "flash_attn.kpm", dtype=torch.uint8)
-        assert kpm.numel() == N * Lk
-    O = torch.empty(N, Lq, H * 32, dtype=_F32, device=Q.device)
-    lse = torch.empty(N, H, Lq, dtype=_F32, device=Q.device)
-    lib.call("cape_flash_attn_fwd", _p(Q), _p(K), _p(V), _p(O), _p(lse), _ld(Q), _ld(K), _ld(V), H * 32, Q.stride(0), K.stride(0),
-             V.stride(0), Lq * H * 32, N, H, Lq, Lk, float(scale), mask_mode, causal_offset, _p(kpm), float(dropout_p),
-             rng.ptr if (rng is not None and dropout_p > 0) else None, rng_stream, _stream())
-    return O, lse
+    return _attn_fwd(True, Q, K, V, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream)
 
 
 def flash_attn_bwd(dO, Q, K, V, O, lse, dQ, dK, dV, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=None, dropout_p=0.0,
                    rng=None, rng_stream=0):
-    _flash_views(Q, K, V, N, H, Lq, Lk)
-    _flash_views(dQ, dK, dV, N, H, Lq, Lk)
-    _chk(dO, "flash_attn_bwd.dO"); _chk(O, "flash_attn_bwd.O"); _chk(lse, "flash_attn_bwd.lse")
-    assert dO.shape == O.shape == (N, Lq, H * 32) and lse.numel() == N * H * Lq
-    assert _ld(dQ) == _ld(Q) and _ld(dK) == _ld(K) and _ld(dV) == _ld(V)
-    assert dQ.stride(0) == Q.stride(0) and dK.stride(0) == K.stride(0) and dV.stride(0) == V.stride(0)
-    ws = torch.empty(N * H * Lq, dtype=_F32, device=dO.device)
-    lib.call("cape_flash_attn_bwd", _p(dO), _p(Q), _p(K), _p(V), _p(O), _p(lse), _p(dQ), _p(dK), _p(dV), _p(ws), _ld(Q), _ld(K), _ld(V),
-             H * 32, Q.stride(0), K.stride(0), V.stride(0), Lq * H * 32, N, H, Lq, Lk, float(scale), mask_mode, causal_offset, _p(kpm),
-             float(dropout_p), rng.ptr if (rng is not None and dropout_p > 0) else None, rng_stream, _stream())
+    _attn_bwd(True, dO, Q, K, V, O, lse, dQ, dK, dV, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream)
 
 
 def attn_mm_ok(N, H, Lq, Lk):
@@ -619,7 +638,7 @@ def attn_mm_fwd(Q, K, V, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=
     P = torch.empty_like(S)
     Pd = torch.empty_like(S) if dropout_p > 0 else None
     lib.call("cape_attn_softmax_fwd", _p(S), _p(P), _p(Pd), N, H, Lq, Lk, float(scale), mask_mode, causal_offset, _p(kpm),
-             float(dropout_p), rng.ptr if (rng is not None and dropout_p > 0) else None, rng_stream, _stream())
+             float(dropout_p), _rng_ptr(rng, dropout_p), rng_stream, _stream())
     Pu = Pd if Pd is not None else P
     O = torch.empty(N, Lq, H * 32, dtype=_F32, device=dev)
     gemm(Pu, V, O, Lq, 32, Lk, a_mode=0, b_mode=1, lda=Lk, ldb=_ld(V), ldc=H * 32,
@@ -636,24 +655,41 @@ def attn_mm_bwd(dO, Q, K, V, P, Pu, dQ, dK, dV, N, H, Lq, Lk, scale, dropout_p=0
     gemm(dO, V, dS, Lq, Lk, 32, lda=H * 32, ldb=_ld(V), ldc=Lk,
          batch=(N * H, H, Lq * H * 32, 32, V.stride(0), 32, img, blk))
     lib.call("cape_attn_softmax_bwd", _p(P), _p(dS), N, H, Lq, Lk, float(scale), float(dropout_p),
-             rng.ptr if (rng is not None and dropout_p > 0) else None, rng_stream, _stream())
+             _rng_ptr(rng, dropout_p), rng_stream, _stream())
     gemm(dS, K, dQ, Lq, 32, Lk, a_mode=0, b_mode=1, lda=Lk, ldb=_ld(K), ldc=_ld(dQ),
          batch=(N * H, H, img, blk, K.stride(0), 32, dQ.stride(0), 32))
     gemm(dS, Q, dK, Lk, 32, Lq, a_mode=1, b_mode=1, lda=Lk, ldb=_ld(Q), ldc=_ld(dK),
          batch=(N * H, H, img, blk, Q.stride(0), 32, dK.stride(0), 32))
 
 
-def attn_bwd(dO, Q, K, V, O, lse, dQ, dK, dV, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=None, dropout_p=0.0,
-             rng=None, rng_stream=0):
-    _chk(dO, "attn_bwd.dO")
-    for t in (dQ, dK, dV):
-        _chk(t, "attn_bwd.grad", contiguous=False)
-    assert _ld(dQ) == _ld(Q) and _ld(dK) == _ld(K) and _ld(dV) == _ld(V)
-    assert dQ.stride(0) == Q.stride(0) and dK.stride(0) == K.stride(0) and dV.stride(0) == V.stride(0)
-    assert O.is_contiguous() and dO.shape == O.shape
-    lib.call("cape_attn_bwd", _p(dO), _p(Q), _p(K), _p(V), _p(O), _p(lse), _p(dQ), _p(dK), _p(dV), _ld(Q), _ld(K), _ld(V),
-             H * 32, Q.stride(0), K.stride(0), V.stride(0), Lq * H * 32, N, H, Lq, Lk, float(scale), mask_mode, causal_offset, _p(kpm), float(dropout_p),
-             rng.ptr if (rng is not None and dropout_p > 0) else None, rng_stream, _stream())
+def attn_route(N, H, Lq, Lk, flash=False):
+    """THE choice between the three attention implementations, asked once per autograd node: "flash" (fused matrix-core kernels;
+    only for callers that allow it), else "mm" (batched GEMMs around the row softmax), else "scalar" (online-softmax kernels)."""
+    if flash and flash_attn_ok(N, H, Lq, Lk):
+        return "flash"
+    return "mm" if attn_mm_ok(N, H, Lq, Lk) else "scalar"
+
+
+_ATTN_LAUNCHERS = {"scalar": (attn_fwd, attn_bwd), "flash": (flash_attn_fwd, flash_attn_bwd)}
+
+
+def attn_core_fwd(route, Q, K, V, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=None, dropout_p=0.0, rng=None, rng_stream=0):
+    """The attention core on `route` (attn_route's answer, or a literal).  Returns O and the tuple of tensors attn_core_bwd needs
+    besides the operands and O -- (lse,) for "scalar" / "flash", (P, Pu) for "mm" -- which ctx.save_for_backward takes as it is."""
+    if route == "mm":
+        O, P, Pu = attn_mm_fwd(Q, K, V, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream)
+        return O, (P, Pu)
+    O, lse = _ATTN_LAUNCHERS[route][0](Q, K, V, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p, rng, rng_stream)
+    return O, (lse,)
+
+
+def attn_core_bwd(route, saved, dO, Q, K, V, O, dQ, dK, dV, N, H, Lq, Lk, scale, mask_mode=0, causal_offset=0, kpm=None, dropout_p=0.0,
+                  rng=None, rng_stream=0):
+    if route == "mm":
+        attn_mm_bwd(dO, Q, K, V, *saved, dQ, dK, dV, N, H, Lq, Lk, scale, dropout_p, rng, rng_stream)
+    else:
+        _ATTN_LAUNCHERS[route][1](dO, Q, K, V, O, *saved, dQ, dK, dV, N, H, Lq, Lk, scale, mask_mode, causal_offset, kpm, dropout_p,
+                                  rng, rng_stream)
 
 
 # ------------------------------------------------------------------------------------------------
