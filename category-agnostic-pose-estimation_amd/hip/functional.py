@@ -455,94 +455,107 @@ def _w_phys(weight):
     return wp
 
 
+def _conv_stage_fwd(x, weight, scale, shift, residual, stride, pad, relu, allow_split):
+    """One convolution stage, y = act(conv(x) * scale + shift + residual), as a plain function: -> (y, meta, saved).  `meta` is
+    the non-tensor record and `saved` the tensors `_conv_stage_bwd` needs; the calling autograd node hands `saved` to its own
+    save_for_backward (x is (N, H, W, C) NHWC)."""
+    x = _c(x)
+    N, H, W, C = x.shape
+    O, C2, KH, KW = weight.shape
+    assert C2 == C
+    wp = _w_phys(weight)
+    OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    M, K = N * OH * OW, KH * KW * C
+    y = torch.empty(N, OH, OW, O, dtype=torch.float32, device=x.device)
+    res = _c(residual) if residual is not None else None
+    geom = (N, H, W, C, KH, KW, stride, pad, OH, OW, O)
+    dense = KH == 1 and KW == 1 and stride == 1 and pad == 0
+    # few output tiles over a deep contraction (the 3x3/s2 input_proj conv on C5: 512 x 256 x 18432 = 32 tiles; the 3x3
+    # convolutions of layer4: 2048 x 512 x 4608 = 256 tiles of 144 k-tiles each): split K over blocks (atomic partial sums,
+    # the bias rides with the first split) and apply FrozenBN / ReLU / shortcut in a separate in-place pass.  Training
+    # only: the atomic k-split sums in arrival order, and inference keeps run-to-run bitwise reproducibility (the
+    # replayed decode graphs are tested bit-for-bit against the eager loop).
+    # (`allow_split` = grad mode at the call site: autograd runs Function.forward itself with grad mode off)
+    sk = ops.pick_split_k(M, O, K) if (allow_split and not _DETERMINISTIC) else 1
+    plain = scale is None and res is None and not relu
+    sk = sk if (sk >= 8 or (sk >= 4 and not plain)) else 1
+    if sk > 1:
+        y.zero_()
+        kw = dict(bias=shift if plain else None, split_k=sk, accumulate=True)
+    else:
+        kw = dict(scale=scale, bias=shift, residual=res, relu=relu)
+    if dense:
+        ops.gemm(x, wp, y, M, O, K, **kw)
+    else:
+        ops.gemm(x, wp, y, M, O, K, a_mode=2, b_mode=0, conv=geom, **kw)
+    if sk > 1 and not plain:
+        ops.affine_act_(y, scale, shift, res, relu)
+    return y, (geom, dense, relu, residual is not None), (x, weight, scale, y if relu else None)
+
+
+def _conv_stage_bwd(meta, saved, dy, w_ref, shift_ref=None, *, need_x, need_w=False, need_shift=False, need_res=False, acc_dx=None):
+    """Backward of one `_conv_stage_fwd` call: -> (dx, dw, dshift, dres), each None unless its need_* is set.  `w_ref` /
+    `shift_ref`: the parameters as the node received them (`_ParamGrads` finds their gradient-arena views).  `acc_dx`: a
+    gradient of the same input that already exists (the bottleneck's shortcut branch) -- the data gradient is added into it by
+    the accumulate epilogue instead of a separate summation pass, and it is returned as dx."""
+    x, weight, scale, y = saved
+    geom, dense, relu, has_res = meta
+    N, H, W, C, KH, KW, stride, pad, OH, OW, O = geom
+    dy = _c(dy)
+    M, K = N * OH * OW, KH * KW * C
+    want_res = has_res and need_res
+    if relu or scale is not None or want_res:
+        dpre, dres = ops.bn_relu_bwd(dy, y if relu else dy, scale, relu, want_res) if scale is not None else \
+            _relu_bwd_noscale(dy, y, relu, want_res)
+    else:
+        dpre, dres = dy, None
+    wp = _w_phys(weight)
+    dx = None
+    if need_x:
+        dx = acc_dx if acc_dx is not None else torch.empty(N, H, W, C, dtype=torch.float32, device=dy.device)
+        if dense:
+            ops.gemm(dpre, wp, dx, M, C, O, a_mode=0, b_mode=1, accumulate=acc_dx is not None)
+        elif _dgrad_stride2_ok(geom):
+            _dgrad_stride2(dpre, wp, geom, dx, acc_dx)
+        else:
+            sk = ops.pick_split_k(N * H * W, C, KH * KW * O)
+            sk = sk if sk >= 4 else 1
+            if sk > 1 and acc_dx is None:
+                dx.zero_()
+            ops.gemm(dpre, wp, dx, N * H * W, C, KH * KW * O, a_mode=3, b_mode=2, conv=geom, split_k=sk,
+                     accumulate=sk > 1 or acc_dx is not None)
+    # the weight gradient is computed in the physical (O, KH, KW, C) layout of the channels_last weight (and of its gradient)
+    pg = _ParamGrads((w_ref, shift_ref), (need_w, need_shift))
+    dw, dshift = pg.bufs
+    src_s = None
+    if dshift is not None:
+        src_s = dpre if scale is None else (dres if dres is not None else _mask_only(dy, y, relu))
+    with pg.side(dpre, x, src_s):
+        fuse_s = src_s is dpre and dw is not None   # the bias sums ride in the wgrad
+        if dw is not None:
+            kw = dict(a_mode=1, lda=O, accumulate=True, colsum_out=dshift if fuse_s else None)
+            if dense:
+                pg.gemm(dpre, x, _w_phys(dw), O, C, M, b_mode=1, ldb=C, split_k=ops.pick_split_k(O, C, M), **kw)
+            else:
+                pg.gemm(dpre, x, _w_phys(dw), O, K, M, b_mode=3, conv=geom, split_k=ops.pick_split_k(O, K, M), **kw)
+        if dshift is not None and not fuse_s:
+            ops.colsum(src_s, M, O, dshift)
+    return (dx,) + pg.result() + (dres,)
+
+
 class ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, scale, shift, residual, stride, pad, relu, allow_split=False):
-        # x (N, H, W, C) contiguous NHWC
-        x = _c(x)
-        N, H, W, C = x.shape
-        O, C2, KH, KW = weight.shape
-        assert C2 == C
-        wp = _w_phys(weight)
-        OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-        M, K = N * OH * OW, KH * KW * C
-        y = torch.empty(N, OH, OW, O, dtype=torch.float32, device=x.device)
-        res = _c(residual) if residual is not None else None
-        geom = (N, H, W, C, KH, KW, stride, pad, OH, OW, O)
-        dense = KH == 1 and KW == 1 and stride == 1 and pad == 0
-        # few output tiles over a deep contraction (the 3x3/s2 input_proj conv on C5: 512 x 256 x 18432 = 32 tiles; the 3x3
-        # convolutions of layer4: 2048 x 512 x 4608 = 256 tiles of 144 k-tiles each): split K over blocks (atomic partial sums,
-        # the bias rides with the first split) and apply FrozenBN / ReLU / shortcut in a separate in-place pass.  Training
-        # only: the atomic k-split sums in arrival order, and inference keeps run-to-run bitwise reproducibility (the
-        # replayed decode graphs are tested bit-for-bit against the eager loop).
-        # (`allow_split` = grad mode at the call site: autograd runs Function.forward itself with grad mode off)
-        sk = ops.pick_split_k(M, O, K) if (allow_split and not _DETERMINISTIC) else 1
-        plain = scale is None and res is None and not relu
-        sk = sk if (sk >= 8 or (sk >= 4 and not plain)) else 1
-        if sk > 1:
-            y.zero_()
-            kw = dict(bias=shift if plain else None, split_k=sk, accumulate=True)
-        else:
-            kw = dict(scale=scale, bias=shift, residual=res, relu=relu)
-        if dense:
-            ops.gemm(x, wp, y, M, O, K, **kw)
-        else:
-            ops.gemm(x, wp, y, M, O, K, a_mode=2, b_mode=0, conv=geom, **kw)
-        if sk > 1 and not plain:
-            ops.affine_act_(y, scale, shift, res, relu)
-        ctx.save_for_backward(x, weight, scale, y if relu else None)
+        y, ctx.meta, saved = _conv_stage_fwd(x, weight, scale, shift, residual, stride, pad, relu, allow_split)
+        ctx.save_for_backward(*saved)
         ctx.w_ref, ctx.shift_ref = weight, shift
-        ctx.meta = (geom, dense, relu, shift is not None, residual is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight, scale, y = ctx.saved_tensors
-        geom, dense, relu, has_shift, has_res = ctx.meta
-        N, H, W, C, KH, KW, stride, pad, OH, OW, O = geom
-        dy = _c(dy)
-        M, K = N * OH * OW, KH * KW * C
-        want_res = has_res and ctx.needs_input_grad[4]
-        if relu or scale is not None or want_res:
-            dpre, dres = ops.bn_relu_bwd(dy, y if relu else dy, scale, relu, want_res) if scale is not None else \
-                _relu_bwd_noscale(dy, y, relu, want_res)
-        else:
-            dpre, dres = dy, None
-        wp = _w_phys(weight)
-        dx = dw = dshift = None
-        if ctx.needs_input_grad[0]:
-            # `accum_dx` (set by BottleneckFn): a gradient of the same input that already exists (the shortcut branch's) --
-            # the data gradient is added into it by the accumulate epilogue instead of a separate summation pass
-            acc_dx = getattr(ctx, "accum_dx", None)
-            dx = acc_dx if acc_dx is not None else torch.empty(N, H, W, C, dtype=torch.float32, device=dy.device)
-            if dense:
-                ops.gemm(dpre, wp, dx, M, C, O, a_mode=0, b_mode=1, accumulate=acc_dx is not None)
-            elif _dgrad_stride2_ok(geom):
-                _dgrad_stride2(dpre, wp, geom, dx, acc_dx)
-            else:
-                sk = ops.pick_split_k(N * H * W, C, KH * KW * O)
-                sk = sk if sk >= 4 else 1
-                if sk > 1 and acc_dx is None:
-                    dx.zero_()
-                ops.gemm(dpre, wp, dx, N * H * W, C, KH * KW * O, a_mode=3, b_mode=2, conv=geom, split_k=sk,
-                         accumulate=sk > 1 or acc_dx is not None)
-        # the weight gradient is computed in the physical (O, KH, KW, C) layout of the channels_last weight (and of its gradient)
-        pg = _ParamGrads((ctx.w_ref, ctx.shift_ref), (ctx.needs_input_grad[1], has_shift and ctx.needs_input_grad[3]))
-        dw, dshift = pg.bufs
-        src_s = None
-        if dshift is not None:
-            src_s = dpre if scale is None else (dres if dres is not None else _mask_only(dy, y, relu))
-        with pg.side(dpre, x, src_s):
-            fuse_s = src_s is dpre and dw is not None   # the bias sums ride in the wgrad
-            if dw is not None:
-                kw = dict(a_mode=1, lda=O, accumulate=True, colsum_out=dshift if fuse_s else None)
-                if dense:
-                    pg.gemm(dpre, x, _w_phys(dw), O, C, M, b_mode=1, ldb=C, split_k=ops.pick_split_k(O, C, M), **kw)
-                else:
-                    pg.gemm(dpre, x, _w_phys(dw), O, K, M, b_mode=3, conv=geom, split_k=ops.pick_split_k(O, K, M), **kw)
-            if dshift is not None and not fuse_s:
-                ops.colsum(src_s, M, O, dshift)
-        dw, dshift = pg.result()
+        need_x, need_w, _, need_shift, need_res = ctx.needs_input_grad[:5]
+        dx, dw, dshift, dres = _conv_stage_bwd(ctx.meta, ctx.saved_tensors, dy, ctx.w_ref, ctx.shift_ref, need_x=need_x,
+                                               need_w=need_w, need_shift=need_shift, need_res=need_res)
         return dx, dw, None, dshift, dres, None, None, None, None
 
 
@@ -600,80 +613,43 @@ def _mask_only(dy, y, relu):
     return ops.relu_drop_bwd(dy, y, 1.0) if relu else dy
 
 
-class _PlainCtx:
-    """Stand-in for an autograd context when one Function runs several ConvFn stages itself."""
-
-    def __init__(self, needs_input_grad):
-        self.needs_input_grad = needs_input_grad
-        self.saved_tensors = ()
-        self.accum_dx = None
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
-
-
 class BottleneckFn(torch.autograd.Function):
     """torchvision Bottleneck v1.5 with FrozenBatchNorm2d (reference backbone.py:20-57 over torchvision.models.resnet50) as ONE
     autograd node: conv1-bn-relu, conv2(3x3, stride)-bn-relu, [downsample conv-bn], conv3-bn + shortcut + relu.  The backward
-    runs the four ConvFn stages in order and lets conv1's data gradient accumulate into the shortcut's gradient (the block
+    runs the four conv stages in order and lets conv1's data gradient accumulate into the shortcut's gradient (the block
     input has two consumers; as separate nodes their gradients cost a summation pass over the largest tensors of the trunk),
     and the host pays for one node instead of five."""
 
     @staticmethod
     def forward(ctx, x, w1, w2, w3, wd, s1, b1, s2, b2, s3, b3, sd, bd, stride, allow_split):
-        nx = ctx.needs_input_grad[0]
-        c1 = _PlainCtx((nx, w1.requires_grad, False, False, False))
-        o1 = ConvFn.forward(c1, x, w1, s1, b1, None, 1, 0, True, allow_split)
-        c2 = _PlainCtx((True, w2.requires_grad, False, False, False))
-        o2 = ConvFn.forward(c2, o1, w2, s2, b2, None, stride, 1, True, allow_split)
-        cd, idt = None, x
+        o1, m1, t1 = _conv_stage_fwd(x, w1, s1, b1, None, 1, 0, True, allow_split)
+        o2, m2, t2 = _conv_stage_fwd(o1, w2, s2, b2, None, stride, 1, True, allow_split)
+        idt, md, td = x, None, ()
         if wd is not None:
-            cd = _PlainCtx((nx, wd.requires_grad, False, False, False))
-            idt = ConvFn.forward(cd, x, wd, sd, bd, None, stride, 0, False, allow_split)
-        c3 = _PlainCtx((True, w3.requires_grad, False, False, nx or wd is not None))
-        y = ConvFn.forward(c3, o2, w3, s3, b3, idt, 1, 0, True, allow_split)
-        # every tensor the four stages keep goes through the node's own save_for_backward: the block output `y` is among them
-        # (conv3's ReLU mask), and an output held as a plain attribute of the context is a reference cycle through its grad_fn
-        # that Python's collector cannot see -- round 2 leaked ~1.4 GiB of trunk activations per training step that way
-        flat, spans = [], []
-        for c in (c1, c2, c3, cd):
-            if c is None:
-                spans.append(None)
-                continue
-            spans.append((len(flat), len(c.saved_tensors)))
-            flat.extend(c.saved_tensors)
-            c.saved_tensors = ()
-        ctx.save_for_backward(*flat)
-        ctx.sub = (c1, c2, c3, cd)
-        ctx.spans = spans
+            idt, md, td = _conv_stage_fwd(x, wd, sd, bd, None, stride, 0, False, allow_split)
+        y, m3, t3 = _conv_stage_fwd(o2, w3, s3, b3, idt, 1, 0, True, allow_split)
+        # every tensor the four stages keep goes through the node's own save_for_backward: the block output `y` is among
+        # them (conv3's ReLU mask), and an output held as a plain attribute of the context is a reference cycle through its
+        # grad_fn that Python's collector cannot see -- round 2 leaked ~1.4 GiB of trunk activations per training step that way
+        ctx.save_for_backward(*t1, *t2, *t3, *td)
+        ctx.cuts = (len(t1), len(t1) + len(t2), len(t1) + len(t2) + len(t3))
+        ctx.metas = (m1, m2, m3, md)
+        ctx.w_refs = (w1, w2, w3, wd)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        c1, c2, c3, cd = ctx.sub
-        saved = ctx.saved_tensors
-        for c, sp in zip(ctx.sub, ctx.spans):
-            if c is not None:
-                c.saved_tensors = tuple(saved[sp[0]:sp[0] + sp[1]])
-        try:
-            return BottleneckFn._backward(ctx, dy)
-        finally:
-            for c in ctx.sub:                           # nothing of this pass stays on the long-lived stage contexts
-                if c is not None:
-                    c.saved_tensors, c.accum_dx = (), None
-
-    @staticmethod
-    def _backward(ctx, dy):
-        c1, c2, c3, cd = ctx.sub
-        d2, dw3, _, _, dres = ConvFn.backward(c3, dy)[:5]
-        d1, dw2 = ConvFn.backward(c2, d2)[:2]
-        dwd = None
-        if cd is not None:
-            dxd, dwd = ConvFn.backward(cd, dres)[:2]
-            c1.accum_dx = dxd                       # None when the block input needs no gradient
-        else:
-            c1.accum_dx = dres if c1.needs_input_grad[0] else None
-        dx, dw1 = ConvFn.backward(c1, d1)[:2]
+        t, (a, b, c) = ctx.saved_tensors, ctx.cuts
+        t1, t2, t3, td = t[:a], t[a:b], t[b:c], t[c:]
+        m1, m2, m3, md = ctx.metas
+        w1, w2, w3, wd = ctx.w_refs
+        need_x, need_w1, need_w2, need_w3, need_wd = ctx.needs_input_grad[:5]
+        d2, dw3, _, dres = _conv_stage_bwd(m3, t3, dy, w3, need_x=True, need_w=need_w3, need_res=need_x or wd is not None)
+        d1, dw2, _, _ = _conv_stage_bwd(m2, t2, d2, w2, need_x=True, need_w=need_w2)
+        dwd, dshort = None, (dres if need_x else None)       # the block input's gradient through the shortcut
+        if wd is not None:
+            dshort, dwd, _, _ = _conv_stage_bwd(md, td, dres, wd, need_x=need_x, need_w=need_wd)
+        dx, dw1, _, _ = _conv_stage_bwd(m1, t1, d1, w1, need_x=need_x, need_w=need_w1, acc_dx=dshort)
         return (dx, dw1, dw2, dw3, dwd) + (None,) * 10
 
 

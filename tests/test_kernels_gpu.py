@@ -226,6 +226,109 @@ def test_conv_stride2_dgrad_by_parity_classes(N, H, W, C, O, k, pad, acc):
     close(dx - (base if acc else 0.0), one.view(N, H, W, C), tol=2e-5, name="classes vs one gather launch")
 
 
+def _bottleneck_case(inplanes, planes, proj, seed=0):
+    """CPU fp32 weights (w1, w2, w3, wd | None) and folded FrozenBN (scale, shift) pairs (bn1, bn2, bn3, bnd | None)."""
+    outp = planes * 4
+    shapes = [(planes, inplanes, 1), (planes, planes, 3), (outp, planes, 1)] + ([(outp, inplanes, 1)] if proj else [])
+    ws = [rnd(o, c, k, k, seed=seed + 10 * i, scale=(c * k * k) ** -0.5) for i, (o, c, k) in enumerate(shapes)]
+    bns = [(rnd(o, seed=seed + 10 * i + 1).abs() + 0.5, rnd(o, seed=seed + 10 * i + 2)) for i, (o, c, k) in enumerate(shapes)]
+    return ws + [None] * (4 - len(ws)), bns + [None] * (4 - len(bns))
+
+
+@pytest.mark.parametrize("proj,stride,need_x", [(True, 2, False), (True, 2, True), (True, 1, True), (False, 1, True)])
+def test_bottleneck_node_matches_conv_chain_and_torch(proj, stride, need_x):
+    """HF.bottleneck (one autograd node over four conv stages; conv1's data gradient accumulates into the shortcut's) against
+    the same block as four HF.conv_bn_act nodes (autograd sums the block input's two gradients) and against torch fp32 on the
+    CPU (torchvision Bottleneck v1.5 over FrozenBatchNorm2d, ref backbone.py:20-57): projection shortcut at stride 2 behind a
+    frozen input (layer2's first block) and with an input gradient, projection at stride 1, identity shortcut.  The 3x3 at
+    stride 2 and the stride-2 projection take the parity-class data gradient, the 3x3 at stride 1 the gather form."""
+    from cape_amd.hip import functional as HF
+    N, H, planes = 2, 16, 64
+    inplanes = 128 if proj else planes * 4
+    ws, bns = _bottleneck_case(inplanes, planes, proj)
+    OH = H // stride
+    if stride == 2:
+        assert HF._dgrad_stride2_ok((N, H, H, planes, 3, 3, 2, 1, OH, OH, planes))
+        assert HF._dgrad_stride2_ok((N, H, H, inplanes, 1, 1, 2, 0, OH, OH, planes * 4))
+    x = rnd(N, inplanes, H, H, seed=5)
+    g = rnd(N, planes * 4, OH, OH, seed=9)
+
+    def affine(t, bn):
+        return t * bn[0].view(1, -1, 1, 1) + bn[1].view(1, -1, 1, 1)
+
+    xr = x.clone().requires_grad_(need_x)
+    wr = [w.clone().requires_grad_(True) if w is not None else None for w in ws]
+    o = F.relu(affine(F.conv2d(xr, wr[0]), bns[0]))
+    o = F.relu(affine(F.conv2d(o, wr[1], stride=stride, padding=1), bns[1]))
+    idt = affine(F.conv2d(xr, wr[3], stride=stride), bns[3]) if proj else xr
+    y_ref = F.relu(affine(F.conv2d(o, wr[2]), bns[2]) + idt)
+    y_ref.backward(g)
+
+    def device_inputs():
+        xn = x.permute(0, 2, 3, 1).contiguous().to(DEV).requires_grad_(need_x)
+        wn = [torch.nn.Parameter(w.to(DEV).contiguous(memory_format=torch.channels_last)) if w is not None else None for w in ws]
+        bn = [(b[0].to(DEV), b[1].to(DEV)) if b is not None else None for b in bns]
+        return xn, wn, bn
+
+    gn = g.permute(0, 2, 3, 1).contiguous().to(DEV)
+    xb, wb, bn = device_inputs()
+    y_node = HF.bottleneck(xb, wb[0], wb[1], wb[2], wb[3], bn[0], bn[1], bn[2], bn[3], stride)
+    y_node.backward(gn)
+    xc, wc, bn = device_inputs()
+    o = HF.conv_bn_act(xc, wc[0], *bn[0], relu=True)
+    o = HF.conv_bn_act(o, wc[1], *bn[1], stride=stride, pad=1, relu=True)
+    idt = HF.conv_bn_act(xc, wc[3], *bn[3], stride=stride) if proj else xc
+    y_chain = HF.conv_bn_act(o, wc[2], *bn[2], relu=True, residual=idt)
+    y_chain.backward(gn)
+    HF.Runtime.join()
+
+    close(y_node.permute(0, 3, 1, 2), y_ref, name="bottleneck fwd vs torch")
+    close(y_node, y_chain, name="bottleneck fwd vs conv chain")
+    for what, xd, wd in (("node", xb, wb), ("chain", xc, wc)):
+        if need_x:
+            close(xd.grad.permute(0, 3, 1, 2), xr.grad, tol=2e-4, name=f"{what} input gradient vs torch")
+        else:
+            assert xd.grad is None
+        for i, (w, r) in enumerate(zip(wd, wr)):
+            if w is not None:
+                close(w.grad, r.grad, tol=2e-4, name=f"{what} weight gradient {i} vs torch")
+    if need_x:
+        close(xb.grad, xc.grad, tol=2e-4, name="input gradient node vs chain")
+    for i, (a, b) in enumerate(zip(wb, wc)):
+        if a is not None:
+            close(a.grad, b.grad, tol=2e-4, name=f"weight gradient {i} node vs chain")
+
+
+def test_bottleneck_node_releases_its_activations():
+    """A bottleneck node's activations die with the last reference to its output, without the cycle collector: every tensor the
+    node keeps goes through save_for_backward.  (An output held as a plain context attribute is a cycle through its grad_fn;
+    each round would then leave its activations allocated.)"""
+    import gc
+    from cape_amd.hip import functional as HF
+    ws, bns = _bottleneck_case(128, 64, True)
+    wn = [torch.nn.Parameter(w.to(DEV).contiguous(memory_format=torch.channels_last)) for w in ws]
+    bn = [(b[0].to(DEV), b[1].to(DEV)) for b in bns]
+    gc_was_on = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        allocated = []
+        for i in range(3):
+            xn = rnd(2, 16, 16, 128, seed=20 + i).to(DEV).requires_grad_(True)
+            y = HF.bottleneck(xn, wn[0], wn[1], wn[2], wn[3], bn[0], bn[1], bn[2], bn[3], 2)
+            y.backward(rnd(*y.shape, seed=30 + i).to(DEV))
+            HF.Runtime.join()                               # side-stream readers are kept alive until the join
+            del xn, y
+            for w in wn:
+                w.grad = None
+            torch.cuda.synchronize()
+            allocated.append(torch.cuda.memory_allocated())
+        assert allocated[2] == allocated[1], allocated
+    finally:
+        if gc_was_on:
+            gc.enable()
+
+
 # ---- fragment-packed weights of the register-stationary kernel (cape_pack_weights, ops.PackedWeights) ----
 @pytest.mark.parametrize("M,N,K,bm", [(5000, 256, 256, 0), (700, 384, 256, 1), (6400, 1024, 256, 0), (333, 100, 128, 1), (4097, 64, 64, 0),
                                       (6400, 70, 256, 0), (400, 70, 256, 0), (129, 33, 64, 1)])
