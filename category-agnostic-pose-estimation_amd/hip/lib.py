@@ -91,6 +91,9 @@ class AugItem(ctypes.Structure):
 DECODE_MAX_LAYERS = 8
 GEMM_GROUP_MAX = 32          # CAPE_GEMM_GROUP_MAX
 SUMSQ_PARTS = 256            # CAPE_SUMSQ_PARTS
+# row of the step-guard ring (CAPE_GUARD_ROW_*): serial and ok are int32 bit patterns, the rest float32
+GUARD_ROW_SERIAL, GUARD_ROW_OK, GUARD_ROW_TOTAL, GUARD_ROW_NORM, GUARD_ROW_COEF, GUARD_ROW_LR, GUARD_ROW_LOSSES = range(7)
+GUARD_NO_STEP = -1.0         # CAPE_GUARD_NO_STEP
 
 
 class DecodeLayerDesc(ctypes.Structure):
@@ -185,6 +188,8 @@ _SIGS = {
     "cape_sumsq": [P, LL, P, P],
     "cape_adamw_step": [P, P, P, P, LL, F, F, F, F, F, F, P, I, P, P, P],
     "cape_step_increment": [P, P],
+    "cape_step_guard": [P, P, I, P, I, F, P, P, P, P, P, I, I, P],
+    "cape_adamw_step_guarded": [P, P, P, P, LL, F, F, F, F, F, F, P, I, P, P, P, P],
     "cape_decode_next_tokens": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "cape_decode_advance": [P, LL, P, LL, P, P, P, I, I, I, I, I, I, I, P, I, I, P, P, P],
     "cape_decode_linear": [POINTER(DecodeLinearDesc), P],

@@ -1177,6 +1177,39 @@ def step_increment(step_t):
     lib.call("cape_step_increment", _p(step_t), _stream())
 
 
+def adamw_step_guarded(p, g, m, v, lr, beta1, beta2, eps, wd, max_norm, sumsq_t, step_t, bad_t, lr_dev=None):
+    """`adamw_step` that returns without touching p, m, v while the device flag bad_t[0] (int32, `step_guard`) is set."""
+    for t in (p, g, m, v):
+        _chk(t, "adamw")
+    assert p.numel() == g.numel() == m.numel() == v.numel()
+    _chk(step_t, "adamw.step", dtype=torch.int64)
+    _chk(bad_t, "adamw.bad", dtype=torch.int32, contiguous=False)
+    if lr_dev is not None:
+        _chk(lr_dev, "adamw.lr_dev", contiguous=False)
+        assert lr_dev.numel() == 1
+    n_parts = sumsq_t.numel() if sumsq_t is not None else 0
+    lib.call("cape_adamw_step_guarded", _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
+             float(wd), float(max_norm), _p(sumsq_t), n_parts, _p(step_t), _p(lr_dev), _p(bad_t), _stream())
+
+
+def step_guard(total, losses, sumsq_t, max_norm, lr_dev, step_t, serial_t, bad_t, ring):
+    """One launch of device bookkeeping per training iteration (include/cape_hip.h, cape_step_guard).  `sumsq_t` None: a
+    micro-batch (no optimizer step, "no step" marker in the row).  `ring` None: no row (then total / losses may be None);
+    otherwise a contiguous (ring_len, row) float32 tensor with row >= lib.GUARD_ROW_LOSSES + losses.numel()."""
+    _chk(step_t, "guard.step", dtype=torch.int64)
+    _chk(serial_t, "guard.serial", dtype=torch.int32, contiguous=False)
+    _chk(bad_t, "guard.bad", dtype=torch.int32, contiguous=False)
+    for t, n in ((total, "guard.total"), (losses, "guard.losses"), (sumsq_t, "guard.sumsq"), (ring, "guard.ring")):
+        _chk(t, n)
+    _chk(lr_dev, "guard.lr_dev", contiguous=False)
+    n_losses = losses.numel() if losses is not None else 0
+    ring_len, row = (ring.shape[0], ring.shape[1]) if ring is not None else (0, 0)
+    if ring is not None:
+        assert ring.dim() == 2 and row >= lib.GUARD_ROW_LOSSES + n_losses and total is not None and lr_dev is not None
+    lib.call("cape_step_guard", _p(total), _p(losses), n_losses, _p(sumsq_t), sumsq_t.numel() if sumsq_t is not None else 0,
+             float(max_norm), _p(lr_dev), _p(step_t), _p(serial_t), _p(bad_t), _p(ring), ring_len, row, _stream())
+
+
 def decode_next_tokens(cls_logits, reg, unfinished_i32, tok_i64, delta, step_i32, N, num_bins, min_len, eos, sep, pad):
     _chk(cls_logits, "next.cls"); _chk(reg, "next.reg"); _chk(delta, "next.delta")
     _chk(unfinished_i32, "next.unfinished", dtype=torch.int32); _chk(tok_i64, "next.tok", dtype=torch.int64)

@@ -61,12 +61,21 @@ def _scaled_dicts(loss_dict, weight_dict):
 
 def train_one_epoch_episodic(model: torch.nn.Module, criterion: torch.nn.Module, data_loader: Iterable,
                              optimizer: torch.optim.Optimizer, device: torch.device, epoch: int, max_norm: float = 0,
-                             print_freq: int = 10, accumulation_steps: int = 1, scaler=None, ddp=None):
+                             print_freq: int = 10, accumulation_steps: int = 1, scaler=None, ddp=None, graph_step=None):
     """One epoch of episodic training with gradient accumulation.  `optimizer` is an `ArenaAdamW`
     (clipping happens inside its fused step; `max_norm` is forwarded to it); `ddp` an optional
     `EpisodeDataParallel`.  `scaler` must be None: the MI355X path keeps fp32 storage and accumulation, with the GEMMs as a
     bf16x3 split by default (CAPE_GEMM_PRECISION=f32 selects exact fp32 MFMA); plain fp16/bf16 autocast misses the parity
-    bar of 1e-3 on logits."""
+    bar of 1e-3 on logits.
+
+    `graph_step` (a `runtime.graph_step.GraphedTrainStep` over a guarded `ArenaAdamW`, built by `run_training` when
+    CAPE_GRAPH_STEP=1) runs every iteration as a captured step and removes the per-iteration host sync: the loop feeds it batches
+    and boundary flags and reads each iteration's losses from the guard's device ring ONE ITERATION LATE; the rows still in
+    flight when the loader ends are drained, so the epoch averages cover every iteration.  The finite-loss check moves with
+    it: a non-finite loss (or gradient norm) makes the device skip that optimizer step and every later one, and the host --
+    which learns of it from the row -- prints what the eager loop prints and exits with status 1 one iteration AFTER the bad
+    one.  The parameters and moments are then those from before the bad step (the eager loop stops before its backward pass,
+    with the same parameters), the step counter counts the applied steps only, and the gradient arenas are zero."""
     if scaler is not None:
         raise ValueError("a GradScaler has no role on the MI355X path: --use_amp selects bf16 MFMA products with fp32 accumulation "
                          "(run_training), which need no loss scaling")
@@ -79,6 +88,9 @@ def train_one_epoch_episodic(model: torch.nn.Module, criterion: torch.nn.Module,
     optimizer.zero_grad()
     world_scale = ddp.loss_scale if ddp is not None else 1.0
     rng = HF.Runtime.get_rng(device)
+    if graph_step is not None:
+        return _train_epoch_graphed(graph_step, criterion, data_loader, optimizer, device, epoch, print_freq, accumulation_steps,
+                                    metric_logger)
     n_batches = 0
     pending = 0
 
@@ -120,6 +132,57 @@ def train_one_epoch_episodic(model: torch.nn.Module, criterion: torch.nn.Module,
             ddp.finish()
         optimizer.step()
         optimizer.zero_grad()
+    metric_logger.synchronize_between_processes()
+    return {k: m.global_avg for k, m in metric_logger.meters.items()}
+
+
+def _train_epoch_graphed(step, criterion, data_loader, optimizer, device, epoch, print_freq, accumulation_steps, metric_logger):
+    """The loop of `train_one_epoch_episodic` over a GraphedTrainStep (see its docstring for the lag and the stop)."""
+    if step.reader is None:
+        raise ValueError("graph_step needs a guarded optimizer: ArenaAdamW(..., guard=StepGuard(...))")
+    if step.accumulation_steps != accumulation_steps:
+        raise ValueError(f"graph_step scales the loss for {step.accumulation_steps} accumulation steps, the epoch asks for "
+                         f"{accumulation_steps}")
+    weight_dict = criterion.weight_dict
+    first = step.reader.next_serial              # the ring's serial of this epoch's iteration 0
+
+    def consume(rows):
+        for row in rows:
+            it = row.serial - first
+            plain = {k: (row.losses[i] if i is not None else 0.0) for k, i in step.row_keys}
+            plain["_ok"] = float(row.ok)
+            if utils.get_world_size() > 1:      # the collective of _scaled_dicts, once per iteration on every rank
+                red = utils.reduce_dict({k: torch.tensor(v, dtype=torch.float32, device=device) for k, v in plain.items()})
+                plain = {k: float(v) for k, v in red.items()}
+            ok = plain.pop("_ok") >= 1.0
+            scaled = {k: v * weight_dict[k] for k, v in plain.items() if k in weight_dict}
+            unscaled = {f"{k}_unscaled": v for k, v in plain.items()}
+            loss_value = float(sum(scaled.values()))
+            if not ok or not math.isfinite(loss_value):
+                print(f"Loss is {loss_value}, stopping training")
+                print(plain)
+                if row.grad_norm is not None and not math.isfinite(row.grad_norm):
+                    print(f"gradient norm is {row.grad_norm}")
+                sys.exit(1)
+            metric_logger.update(loss=loss_value, **scaled, **unscaled)
+            metric_logger.update(lr=row.lr)
+            if print_freq and it % print_freq == 0 and utils.is_main_process():
+                print(f"Epoch [{epoch}] it {it}: loss {loss_value:.4f} lr {row.lr:.6f}")
+
+    pending = 0
+    for batch_idx, batch in enumerate(data_loader):
+        support_coords, support_masks, query_images, skeletons, targets = _to_device(batch, device)
+        boundary = (batch_idx + 1) % accumulation_steps == 0
+        step(query_images, support_coords, support_masks, targets, skeletons, boundary=boundary)
+        pending = 0 if boundary else pending + 1
+        consume(step.reader.poll())             # iteration batch_idx - 1; never waits on the call just enqueued
+    if pending:
+        step.flush()                            # tail flush of engine_cape.py:280-295
+    consume(step.reader.drain())
+    if pending and step.guard.is_bad():         # the flush writes no row: a non-finite accumulated gradient shows in the flag alone
+        print("Loss is nan, stopping training")
+        print("non-finite gradient norm in the tail flush")
+        sys.exit(1)
     metric_logger.synchronize_between_processes()
     return {k: m.global_avg for k, m in metric_logger.meters.items()}
 
@@ -323,8 +386,14 @@ def run_training(args):
                                                num_workers=args.num_workers, drop_last=True, pin_memory=True)
     val_loader = torch.utils.data.DataLoader(val_ds, 1, sampler=vsampler, collate_fn=episodic_collate_fn,
                                              num_workers=args.num_workers, pin_memory=True)
+    graphed = os.environ.get("CAPE_GRAPH_STEP", "0") == "1"
+    guard = None
+    if graphed:
+        # captured training step behind the device-side loss guard (runtime/graph_step.py, runtime/step_guard.py)
+        from ..runtime.step_guard import StepGuard
+        guard = StepGuard(device)
     optimizer = ArenaAdamW(model, lr=args.lr, lr_backbone=args.lr_backbone, weight_decay=args.weight_decay,
-                           max_norm=args.clip_max_norm)
+                           max_norm=args.clip_max_norm, guard=guard)
     if getattr(args, "use_amp", False):
         # the reference's --use_amp = torch.cuda.amp.autocast + GradScaler (engine_cape.py:164-179).  Its MI355X counterpart: every GEMM
         # as ONE bf16 MFMA per product (fp32 master weights, fp32 accumulation, fp32 everything else; bf16 has fp32's exponent range,
@@ -334,6 +403,13 @@ def run_training(args):
         if utils.is_main_process():
             print("--use_amp: GEMMs as single bf16 MFMA products (fp32 accumulate); outside the 1e-3 parity tolerance by design")
     ddp = EpisodeDataParallel(model, optimizer) if world > 1 else None
+    graph_step = None
+    if graphed:
+        from ..runtime.graph_step import GraphedTrainStep
+        graph_step = GraphedTrainStep(model, criterion, optimizer, loss_scale=ddp.loss_scale if ddp is not None else 1.0, ddp=ddp,
+                                      accumulation_steps=args.accumulation_steps)
+        if utils.is_main_process():
+            print("CAPE_GRAPH_STEP=1: captured training step, losses read one iteration late")
     lr_scheduler = build_scheduler(optimizer, args, steps_per_epoch=len(train_loader))
     best_pck, no_improve = 0.0, 0
     if args.resume:
@@ -352,7 +428,7 @@ def run_training(args):
             sampler.set_epoch(epoch)
         t0 = time.time()
         train_stats = train_one_epoch_episodic(model, criterion, train_loader, optimizer, device, epoch, args.clip_max_norm,
-                                               args.print_freq, args.accumulation_steps, None, ddp)
+                                               args.print_freq, args.accumulation_steps, None, ddp, graph_step)
         torch.cuda.synchronize()
         dt = time.time() - t0
         lr_scheduler.step()

@@ -6,7 +6,12 @@
 optimizer, so optimizer checkpoints interchange with `torch.optim.AdamW(param_dicts)` built as in
 `train_cape_episodic.py:527-538`: group 0 = every trainable tensor whose name lacks "backbone" in `named_parameters`
 order -- including the 38 tensors that never receive a gradient, which hold an id but no state --
-group 1 = the backbone tensors."""
+group 1 = the backbone tensors.
+
+`guard=StepGuard(...)` (runtime/step_guard.py, off by default) turns the step into the device-guarded one a captured training
+loop needs: the sum of squares always runs (so `grad_norm()` is current without clipping), `cape_step_guard` books the iteration,
+counts the step and raises the sticky device flag on a non-finite loss or gradient norm, and `cape_adamw_step_guarded` leaves
+parameters and moments alone while that flag is set."""
 import torch
 
 from ..hip import functional as HF
@@ -15,12 +20,13 @@ from .arena import ParamGroupArena, split_groups
 
 
 class ArenaAdamW(torch.optim.Optimizer):
-    def __init__(self, model, lr=1e-4, lr_backbone=1e-5, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=0.0):
+    def __init__(self, model, lr=1e-4, lr_backbone=1e-5, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=0.0, guard=None):
         device = next(model.parameters()).device
         main, backbone, dead = split_groups(model)
         self.arenas = [ParamGroupArena(main, device), ParamGroupArena(backbone, device)]
         self.dead = dead
         self.max_norm = max_norm
+        self.guard = guard
         # reference enumeration: (group, position) -> arena slot or None (a never-trained tensor)
         slot = {id(p): (ai, i) for ai, a in enumerate(self.arenas) for i, p in enumerate(a.params)}
         self._layout = [[], []]
@@ -55,6 +61,8 @@ class ArenaAdamW(torch.optim.Optimizer):
     def step(self, closure=None):
         self.sync_lr()
         HF.Runtime.join()                       # side-stream wgrad kernels must have landed in the arenas
+        if self.guard is not None:
+            return self._guarded_step()
         if self.max_norm > 0:
             for i, a in enumerate(self.arenas):
                 if a.numel:
@@ -67,6 +75,21 @@ class ArenaAdamW(torch.optim.Optimizer):
                                self.max_norm, self.sumsq, self.step_count, lr_dev=self.lr_dev[gi:gi + 1] if self.lr_dev.is_cuda else None)
         # the kernel above rewrote every weight behind autograd's version counters: re-pack the MFMA-fragment copies the
         # register-stationary GEMM reads (one launch over the registered table)
+        ops.PackedWeights.invalidate_and_repack()
+
+    def _guarded_step(self):
+        for i, a in enumerate(self.arenas):
+            if a.numel:
+                ops.sumsq(a.grad, self.sumsq[i * self._parts:(i + 1) * self._parts])
+        self.guard.launch(self, is_step=True)   # row + flag + step count (stands in for step_increment)
+        for gi, (a, g) in enumerate(zip(self.arenas, self.param_groups)):
+            if a.numel:
+                b1, b2 = g["betas"]
+                ops.adamw_step_guarded(a.data, a.grad, a.exp_avg, a.exp_avg_sq, g["lr"], b1, b2, g["eps"], g["weight_decay"],
+                                       self.max_norm, self.sumsq, self.step_count, self.guard.bad,
+                                       lr_dev=self.lr_dev[gi:gi + 1] if self.lr_dev.is_cuda else None)
+        # a skipped step rewrote nothing and the re-pack then reproduces the planes it finds: run it all the same, so the launch
+        # sequence (and a capture of it) does not depend on the flag
         ops.PackedWeights.invalidate_and_repack()
 
     def zero_grad(self, set_to_none=False):

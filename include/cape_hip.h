@@ -528,6 +528,37 @@ int cape_adamw_step(float* p, const float* g, float* m, float* v, long long n, f
 int cape_step_increment(int64_t* step_count, cape_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Device-side loss guard of a captured training step (runtime/graph_step.py): the host no longer reads the loss between
+ * forward and backward, so the bookkeeping and the decision to apply an optimizer step live on the device.
+ *   cape_step_guard (one wave): writes row (serial[0] % ring_len) of `ring` (rows of `row_stride` floats) and bumps serial[0]:
+ *       [ROW_SERIAL] serial (int32 bits)   [ROW_OK] 1 while `bad` is clear after this launch, else 0 (int32 bits)
+ *       [ROW_TOTAL]  total[0]              [ROW_NORM] global gradient norm = sqrt(sum of the n_parts partial sums of cape_sumsq,
+ *                                                     added in cape_adamw_step's order), or CAPE_GUARD_NO_STEP when sumsq_parts
+ *                                                     is NULL (a micro-batch that takes no optimizer step)
+ *       [ROW_COEF]   clip coefficient the step applies (1 when max_norm <= 0)      [ROW_LR] lr_dev[0]
+ *       [ROW_LOSSES + k] losses[k], k < n_losses
+ *     bad[0] is sticky: set when total[0] or the norm is not finite, never cleared here.  step_count[0] += 1 only when
+ *     sumsq_parts is given and bad[0] is clear (this launch stands in for cape_step_increment).  ring == NULL: no row is written
+ *     and serial[0] stays (an optimizer step with no forward pass before it); total/losses/lr_dev may then be NULL.
+ *     Every input is a device pointer or a launch constant: the launch replays from a hipGraph.
+ *   cape_adamw_step_guarded: cape_adamw_step, bit for bit, while bad[0] == 0; no write to p, m, v otherwise.
+ * ---------------------------------------------------------------------------------------------- */
+#define CAPE_GUARD_ROW_SERIAL 0
+#define CAPE_GUARD_ROW_OK 1
+#define CAPE_GUARD_ROW_TOTAL 2
+#define CAPE_GUARD_ROW_NORM 3
+#define CAPE_GUARD_ROW_COEF 4
+#define CAPE_GUARD_ROW_LR 5
+#define CAPE_GUARD_ROW_LOSSES 6
+#define CAPE_GUARD_NO_STEP (-1.0f)
+int cape_step_guard(const float* total, const float* losses, int n_losses, const float* sumsq_parts, int n_parts,
+                    float max_norm, const float* lr_dev, int64_t* step_count, int* serial, int* bad, float* ring,
+                    int ring_len, int row_stride, cape_stream_t stream);
+int cape_adamw_step_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, float max_norm, const float* sumsq_parts, int n_parts,
+                            const int64_t* step_count, const float* lr_dev, const int* bad, cape_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Autoregressive decode bookkeeping on device (roomformer_v2.py:521-598): from the step's class logits
  * (N,3) and coordinates (N,2) produce the next step's 4 token ids + 4 deltas and update the unfinished
  * flags; also appends logits/coords to the per-step output buffers.
