@@ -107,6 +107,9 @@ int launch_mode(const GemmP& p, int a_mode, int b_mode, bool vec, int prec, dim3
 
 extern "C" int cape_gemm_f32(const cape_gemm_desc* d, cape_stream_t stream) {
   CAPE_REQUIRE(d != nullptr, "cape_gemm_f32: null descriptor");
+  // conv dilation (0 = 1): checked first, on the host, before any operand is looked at
+  CAPE_REQUIRE(d->cDil >= 0, "cape_gemm_f32: negative conv dilation (cDil=%d)", d->cDil);
+  CAPE_REQUIRE(d->cDil <= 1 || d->cKHp <= 0, "cape_gemm_f32: conv dilation (cDil=%d) cannot be combined with a tap sub-lattice", d->cDil);
   CAPE_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0, "cape_gemm_f32: negative size");
   if (d->M == 0 || d->N == 0) return 0;
   CAPE_REQUIRE(d->A && d->B && d->C, "cape_gemm_f32: null operand");
@@ -131,6 +134,7 @@ extern "C" int cape_gemm_f32(const cape_gemm_desc* d, cape_stream_t stream) {
   p.A = d->A; p.lda = d->lda; p.B = d->B; p.ldb = d->ldb; p.C = d->C; p.ldc = d->ldc;
   p.cN = d->cN; p.cH = d->cH; p.cW = d->cW; p.cC = d->cC; p.cKH = d->cKH; p.cKW = d->cKW;
   p.cStride = d->cStride; p.cPad = d->cPad; p.cOH = d->cOH; p.cOW = d->cOW; p.cO = d->cO;
+  p.cDil = d->cDil > 0 ? d->cDil : 1;                               // 0 (a zero-initialised descriptor) = 1
   p.scale = d->scale; p.bias = d->bias; p.residual = d->residual; p.ldr = d->ldr;
   p.relu = d->relu; p.accumulate = d->accumulate; p.split_k = d->split_k;
   p.colsum_out = d->colsum_out;

@@ -56,6 +56,7 @@ struct GemmP {
   long long sBias0, sBias1;      // per-batch offsets of `bias`
   // conv-dgrad over a sub-lattice of taps (cape_gemm_desc): column padding, physical filter extent, tap origin / stride
   int cPadX, cKHp, cKWp, cTapH0, cTapHS, cTapW0, cTapWS;
+  int cDil;                      // conv dilation (rows and columns), >= 1: tap (kh, kw) sits (kh * cDil, kw * cDil) pixels from tap (0, 0)
 };
 
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }

@@ -19,13 +19,14 @@ namespace {
 
 constexpr int GROUP_MAX = CAPE_GEMM_GROUP_MAX;
 
-struct GroupItem {                                  // 112 bytes
+struct GroupItem {                                  // 120 bytes
   const float* A; const float* B; float* C; float* colsum_out;
   int M, N, K, split_k;
   int lda, ldb, ldc, tilesM;
   int tilesN, cN, cH, cW;
   int cC, cKH, cKW, cStride;
   int cPad, cOH, cOW, cO;
+  int cDil, pad_;
 };
 
 struct GroupArgs {
@@ -46,6 +47,7 @@ __global__ void __launch_bounds__(256) gemm_group_kernel(const GroupArgs g) {
   p.A = q.A; p.lda = q.lda; p.B = q.B; p.ldb = q.ldb; p.C = q.C; p.ldc = q.ldc;
   p.cN = q.cN; p.cH = q.cH; p.cW = q.cW; p.cC = q.cC; p.cKH = q.cKH; p.cKW = q.cKW;
   p.cStride = q.cStride; p.cPad = q.cPad; p.cOH = q.cOH; p.cOW = q.cOW; p.cO = q.cO;
+  p.cDil = q.cDil;
   p.cPadX = q.cPad; p.cKHp = q.cKH; p.cKWp = q.cKW; p.cTapH0 = 0; p.cTapHS = 1; p.cTapW0 = 0; p.cTapWS = 1;
   p.scale = nullptr; p.bias = nullptr; p.residual = nullptr; p.ldr = 0;
   p.relu = 0; p.accumulate = 1; p.split_k = q.split_k;
@@ -86,6 +88,8 @@ extern "C" int cape_gemm_group_f32(const cape_gemm_desc* descs, int n, int tile,
   long long blocks = 0;
   for (int i = 0; i < n; ++i) {
     const cape_gemm_desc& d = descs[i];
+    CAPE_REQUIRE(d.cDil >= 0, "cape_gemm_group_f32: item %d: negative conv dilation (cDil=%d)", i, d.cDil);
+    CAPE_REQUIRE(d.cDil <= 1 || d.cKHp <= 0, "cape_gemm_group_f32: item %d: conv dilation (cDil=%d) cannot be combined with a tap sub-lattice", i, d.cDil);
     CAPE_REQUIRE(d.a_mode == 1 && d.b_mode == b_mode && d.precision == prec_in, "cape_gemm_group_f32: item %d: mixed modes / precisions", i);
     CAPE_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0 && d.A && d.B && d.C, "cape_gemm_group_f32: item %d: empty product or null operand", i);
     CAPE_REQUIRE(d.accumulate && !d.scale && !d.bias && !d.residual && !d.relu && d.dropout_p == 0.f && !d.mask_src && d.batch <= 1,
@@ -108,6 +112,7 @@ extern "C" int cape_gemm_group_f32(const cape_gemm_desc* descs, int n, int tile,
     q.tilesM = (d.M + tile - 1) / tile; q.tilesN = (d.N + tile - 1) / tile;
     q.cN = d.cN; q.cH = d.cH; q.cW = d.cW; q.cC = d.cC; q.cKH = d.cKH; q.cKW = d.cKW;
     q.cStride = d.cStride; q.cPad = d.cPad; q.cOH = d.cOH; q.cOW = d.cOW; q.cO = d.cO;
+    q.cDil = d.cDil > 0 ? d.cDil : 1; q.pad_ = 0;
     kfull = kfull && (d.K % BK == 0);
     g.bstart[i] = (int)blocks;
     const long long nb = (long long)q.tilesM * q.tilesN * d.split_k;

@@ -100,7 +100,8 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bid) {
   const int b_mc = t % B_CH, b_k0 = t / B_CH;
   constexpr int B_KSTEP = 256 / B_CH;
 
-  // conv gather row decode (AMODE 2: rows are output positions; AMODE 3: rows are input positions)
+  // conv gather row decode (AMODE 2: rows are output positions; AMODE 3: rows are input positions).  Filter tap (kh, kw) of a
+  // convolution with dilation cDil addresses input pixel (oy * stride - pad + kh * cDil, ox * stride - pad + kw * cDil)
   int a_n[NA], a_y[NA], a_x[NA];
   if constexpr (AMODE == 2 || AMODE == 3) {
 #pragma unroll
@@ -218,10 +219,11 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bid) {
       }
     } else if constexpr (AMODE == 2) {
       if (a_fast) {
-        const long long tap_off = ((long long)cv_kh * p.cW + cv_kw) * p.cC + cv_c0;          // uniform
+        const int dkh = cv_kh * p.cDil, dkw = cv_kw * p.cDil;                                // uniform: the tap's pixel offset
+        const long long tap_off = ((long long)dkh * p.cW + dkw) * p.cC + cv_c0;              // uniform
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
-          const int iy = a_y[j] + cv_kh, ix = a_x[j] + cv_kw;
+          const int iy = a_y[j] + dkh, ix = a_x[j] + dkw;
           const bool ok = (a_n[j] >= 0) && (unsigned)iy < (unsigned)p.cH && (unsigned)ix < (unsigned)p.cW;
           const float4 v = *reinterpret_cast<const float4*>(p.A + (ok ? a_base[j] + tap_off : (long long)(4 * a_kc)));
           ra[sl][j] = ok ? v : zero4();
@@ -233,7 +235,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bid) {
       const int kh = tap / p.cKW, kw = tap - kh * p.cKW;
 #pragma unroll
       for (int j = 0; j < NA; ++j) {
-        const int iy = a_y[j] + kh, ix = a_x[j] + kw;
+        const int iy = a_y[j] + kh * p.cDil, ix = a_x[j] + kw * p.cDil;
         const bool ok = (a_n[j] >= 0) && (KFULL || k < p.K) && iy >= 0 && iy < p.cH && ix >= 0 && ix < p.cW;
         const int nn = max(a_n[j], 0), yy = min(max(iy, 0), p.cH - 1), xx = min(max(ix, 0), p.cW - 1);
         const float4 v = *reinterpret_cast<const float4*>(p.A + (((long long)nn * p.cH + yy) * p.cW + xx) * p.cC + c);
@@ -241,10 +243,11 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bid) {
       }
       }
     } else if (a_fast) {  // AMODE == 3, stride 1, O % 32 == 0
-      const long long tap_off = cv_c0 - ((long long)cv_kh * p.cOW + cv_kw) * p.cO;           // uniform
+      const int dkh = cv_kh * p.cDil, dkw = cv_kw * p.cDil;                                  // uniform: the tap's pixel offset
+      const long long tap_off = cv_c0 - ((long long)dkh * p.cOW + dkw) * p.cO;               // uniform
 #pragma unroll
       for (int j = 0; j < NA; ++j) {
-        const int ty = a_y[j] - cv_kh, tx = a_x[j] - cv_kw;
+        const int ty = a_y[j] - dkh, tx = a_x[j] - dkw;
         const bool ok = (a_n[j] >= 0) && (unsigned)ty < (unsigned)p.cOH && (unsigned)tx < (unsigned)p.cOW;
         const float4 v = *reinterpret_cast<const float4*>(p.A + (ok ? a_base[j] + tap_off : (long long)(4 * a_kc)));
         ra[sl][j] = ok ? v : zero4();
@@ -256,7 +259,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bid) {
       const int kh = tap / p.cKW, kw = tap - kh * p.cKW;
 #pragma unroll
       for (int j = 0; j < NA; ++j) {
-        const int ty = a_y[j] - kh, tx = a_x[j] - kw;
+        const int ty = a_y[j] - kh * p.cDil, tx = a_x[j] - kw * p.cDil;
         bool ok = (a_n[j] >= 0) && (KFULL || k < p.K) && ty >= 0 && tx >= 0;
         int oy = ty, ox = tx;
         if (p.cStride != 1) {
@@ -345,7 +348,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bid) {
           oy = tq % p.cOH;
           n = tq / p.cOH;
         }
-        const int iy = oy * p.cStride - p.cPad + kh, ix = ox * p.cStride - p.cPad + kw;
+        const int iy = oy * p.cStride - p.cPad + kh * p.cDil, ix = ox * p.cStride - p.cPad + kw * p.cDil;
         const bool ok = kin && iy >= 0 && iy < p.cH && ix >= 0 && ix < p.cW;
         const int yy = min(max(iy, 0), p.cH - 1), xx = min(max(ix, 0), p.cW - 1);
         const float4 v = *reinterpret_cast<const float4*>(p.B + (((long long)n * p.cH + yy) * p.cW + xx) * p.cC + c);

@@ -455,16 +455,17 @@ def _w_phys(weight):
     return wp
 
 
-def _conv_stage_fwd(x, weight, scale, shift, residual, stride, pad, relu, allow_split):
+def _conv_stage_fwd(x, weight, scale, shift, residual, stride, pad, relu, allow_split, dil=1):
     """One convolution stage, y = act(conv(x) * scale + shift + residual), as a plain function: -> (y, meta, saved).  `meta` is
     the non-tensor record and `saved` the tensors `_conv_stage_bwd` needs; the calling autograd node hands `saved` to its own
-    save_for_backward (x is (N, H, W, C) NHWC)."""
+    save_for_backward (x is (N, H, W, C) NHWC).  `dil`: the convolution's dilation (torch's `dilation=`), kept in `meta` beside the
+    11-tuple geometry."""
     x = _c(x)
     N, H, W, C = x.shape
     O, C2, KH, KW = weight.shape
     assert C2 == C
     wp = _w_phys(weight)
-    OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    OH, OW = (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
     M, K = N * OH * OW, KH * KW * C
     y = torch.empty(N, OH, OW, O, dtype=torch.float32, device=x.device)
     res = _c(residual) if residual is not None else None
@@ -487,10 +488,10 @@ def _conv_stage_fwd(x, weight, scale, shift, residual, stride, pad, relu, allow_
     if dense:
         ops.gemm(x, wp, y, M, O, K, **kw)
     else:
-        ops.gemm(x, wp, y, M, O, K, a_mode=2, b_mode=0, conv=geom, **kw)
+        ops.gemm(x, wp, y, M, O, K, a_mode=2, b_mode=0, conv=geom, conv_dil=dil, **kw)
     if sk > 1 and not plain:
         ops.affine_act_(y, scale, shift, res, relu)
-    return y, (geom, dense, relu, residual is not None), (x, weight, scale, y if relu else None)
+    return y, (geom, dense, relu, residual is not None, dil), (x, weight, scale, y if relu else None)
 
 
 def _conv_stage_bwd(meta, saved, dy, w_ref, shift_ref=None, *, need_x, need_w=False, need_shift=False, need_res=False, acc_dx=None):
@@ -499,7 +500,7 @@ def _conv_stage_bwd(meta, saved, dy, w_ref, shift_ref=None, *, need_x, need_w=Fa
     gradient of the same input that already exists (the bottleneck's shortcut branch) -- the data gradient is added into it by
     the accumulate epilogue instead of a separate summation pass, and it is returned as dx."""
     x, weight, scale, y = saved
-    geom, dense, relu, has_res = meta
+    geom, dense, relu, has_res, dil = meta
     N, H, W, C, KH, KW, stride, pad, OH, OW, O = geom
     dy = _c(dy)
     M, K = N * OH * OW, KH * KW * C
@@ -515,14 +516,14 @@ def _conv_stage_bwd(meta, saved, dy, w_ref, shift_ref=None, *, need_x, need_w=Fa
         dx = acc_dx if acc_dx is not None else torch.empty(N, H, W, C, dtype=torch.float32, device=dy.device)
         if dense:
             ops.gemm(dpre, wp, dx, M, C, O, a_mode=0, b_mode=1, accumulate=acc_dx is not None)
-        elif _dgrad_stride2_ok(geom):
+        elif dil == 1 and _dgrad_stride2_ok(geom):       # (the parity classes are worked out for undilated taps)
             _dgrad_stride2(dpre, wp, geom, dx, acc_dx)
         else:
             sk = ops.pick_split_k(N * H * W, C, KH * KW * O)
             sk = sk if sk >= 4 else 1
             if sk > 1 and acc_dx is None:
                 dx.zero_()
-            ops.gemm(dpre, wp, dx, N * H * W, C, KH * KW * O, a_mode=3, b_mode=2, conv=geom, split_k=sk,
+            ops.gemm(dpre, wp, dx, N * H * W, C, KH * KW * O, a_mode=3, b_mode=2, conv=geom, conv_dil=dil, split_k=sk,
                      accumulate=sk > 1 or acc_dx is not None)
     # the weight gradient is computed in the physical (O, KH, KW, C) layout of the channels_last weight (and of its gradient)
     pg = _ParamGrads((w_ref, shift_ref), (need_w, need_shift))
@@ -537,7 +538,7 @@ def _conv_stage_bwd(meta, saved, dy, w_ref, shift_ref=None, *, need_x, need_w=Fa
             if dense:
                 pg.gemm(dpre, x, _w_phys(dw), O, C, M, b_mode=1, ldb=C, split_k=ops.pick_split_k(O, C, M), **kw)
             else:
-                pg.gemm(dpre, x, _w_phys(dw), O, K, M, b_mode=3, conv=geom, split_k=ops.pick_split_k(O, K, M), **kw)
+                pg.gemm(dpre, x, _w_phys(dw), O, K, M, b_mode=3, conv=geom, conv_dil=dil, split_k=ops.pick_split_k(O, K, M), **kw)
         if dshift is not None and not fuse_s:
             ops.colsum(src_s, M, O, dshift)
     return (dx,) + pg.result() + (dres,)
@@ -545,8 +546,8 @@ def _conv_stage_bwd(meta, saved, dy, w_ref, shift_ref=None, *, need_x, need_w=Fa
 
 class ConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, scale, shift, residual, stride, pad, relu, allow_split=False):
-        y, ctx.meta, saved = _conv_stage_fwd(x, weight, scale, shift, residual, stride, pad, relu, allow_split)
+    def forward(ctx, x, weight, scale, shift, residual, stride, pad, relu, allow_split=False, dilation=1):
+        y, ctx.meta, saved = _conv_stage_fwd(x, weight, scale, shift, residual, stride, pad, relu, allow_split, dilation)
         ctx.save_for_backward(*saved)
         ctx.w_ref, ctx.shift_ref = weight, shift
         return y
@@ -556,7 +557,7 @@ class ConvFn(torch.autograd.Function):
         need_x, need_w, _, need_shift, need_res = ctx.needs_input_grad[:5]
         dx, dw, dshift, dres = _conv_stage_bwd(ctx.meta, ctx.saved_tensors, dy, ctx.w_ref, ctx.shift_ref, need_x=need_x,
                                                need_w=need_w, need_shift=need_shift, need_res=need_res)
-        return dx, dw, None, dshift, dres, None, None, None, None
+        return dx, dw, None, dshift, dres, None, None, None, None, None
 
 
 _DGRAD_S2 = os.environ.get("CAPE_DGRAD_S2_CLASSES", "1") == "1"
@@ -615,15 +616,15 @@ def _mask_only(dy, y, relu):
 
 class BottleneckFn(torch.autograd.Function):
     """torchvision Bottleneck v1.5 with FrozenBatchNorm2d (reference backbone.py:20-57 over torchvision.models.resnet50) as ONE
-    autograd node: conv1-bn-relu, conv2(3x3, stride)-bn-relu, [downsample conv-bn], conv3-bn + shortcut + relu.  The backward
+    autograd node: conv1-bn-relu, conv2(3x3, stride, dilation; padding = dilation)-bn-relu, [downsample conv-bn], conv3-bn + shortcut + relu.  The backward
     runs the four conv stages in order and lets conv1's data gradient accumulate into the shortcut's gradient (the block
     input has two consumers; as separate nodes their gradients cost a summation pass over the largest tensors of the trunk),
     and the host pays for one node instead of five."""
 
     @staticmethod
-    def forward(ctx, x, w1, w2, w3, wd, s1, b1, s2, b2, s3, b3, sd, bd, stride, allow_split):
+    def forward(ctx, x, w1, w2, w3, wd, s1, b1, s2, b2, s3, b3, sd, bd, stride, allow_split, dilation=1):
         o1, m1, t1 = _conv_stage_fwd(x, w1, s1, b1, None, 1, 0, True, allow_split)
-        o2, m2, t2 = _conv_stage_fwd(o1, w2, s2, b2, None, stride, 1, True, allow_split)
+        o2, m2, t2 = _conv_stage_fwd(o1, w2, s2, b2, None, stride, dilation, True, allow_split, dilation)
         idt, md, td = x, None, ()
         if wd is not None:
             idt, md, td = _conv_stage_fwd(x, wd, sd, bd, None, stride, 0, False, allow_split)
@@ -650,17 +651,19 @@ class BottleneckFn(torch.autograd.Function):
         if wd is not None:
             dshort, dwd, _, _ = _conv_stage_bwd(md, td, dres, wd, need_x=need_x, need_w=need_wd)
         dx, dw1, _, _ = _conv_stage_bwd(m1, t1, d1, w1, need_x=need_x, need_w=need_w1, acc_dx=dshort)
-        return (dx, dw1, dw2, dw3, dwd) + (None,) * 10
+        return (dx, dw1, dw2, dw3, dwd) + (None,) * 11
 
 
-def bottleneck(x, w1, w2, w3, wd, bn1, bn2, bn3, bnd, stride):
-    """bnK = (scale, shift) of the folded FrozenBatchNorm2d; wd / bnd = None without a projection shortcut."""
+def bottleneck(x, w1, w2, w3, wd, bn1, bn2, bn3, bnd, stride, dilation=1):
+    """bnK = (scale, shift) of the folded FrozenBatchNorm2d; wd / bnd = None without a projection shortcut.  `dilation`: of the
+    3x3 stage, whose padding equals it (torchvision conv3x3); the three 1x1 stages do not change."""
     sd, bd = bnd if bnd is not None else (None, None)
-    return BottleneckFn.apply(x, w1, w2, w3, wd, bn1[0], bn1[1], bn2[0], bn2[1], bn3[0], bn3[1], sd, bd, int(stride), torch.is_grad_enabled())
+    return BottleneckFn.apply(x, w1, w2, w3, wd, bn1[0], bn1[1], bn2[0], bn2[1], bn3[0], bn3[1], sd, bd, int(stride), torch.is_grad_enabled(),
+                              int(dilation))
 
 
-def conv_bn_act(x, weight, scale, shift, stride=1, pad=0, relu=False, residual=None):
-    return ConvFn.apply(x, weight, scale, shift, residual, int(stride), int(pad), bool(relu), torch.is_grad_enabled())
+def conv_bn_act(x, weight, scale, shift, stride=1, pad=0, relu=False, residual=None, dilation=1):
+    return ConvFn.apply(x, weight, scale, shift, residual, int(stride), int(pad), bool(relu), torch.is_grad_enabled(), int(dilation))
 
 
 # ------------------------------------------------------------------------------------------------

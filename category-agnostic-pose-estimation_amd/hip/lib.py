@@ -46,6 +46,7 @@ class GemmDesc(ctypes.Structure):
         ("sC0", c_longlong), ("sC1", c_longlong),
         ("res_cols", c_int), ("sBias0", c_longlong), ("sBias1", c_longlong),
         ("cPadX", c_int), ("cKHp", c_int), ("cKWp", c_int), ("cTapH0", c_int), ("cTapHS", c_int), ("cTapW0", c_int), ("cTapWS", c_int),
+        ("cDil", c_int),         # conv dilation, appended under ABI 11: 0 = 1
     ]
 
 

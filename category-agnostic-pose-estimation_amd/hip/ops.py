@@ -261,10 +261,13 @@ def gemm(*args, **kw):
 
 def gemm_desc(A, B, C, M, N, K, a_mode=0, b_mode=0, lda=None, ldb=None, ldc=None, bias=None, scale=None, residual=None,
               ldr=None, relu=False, accumulate=False, split_k=1, dropout_p=0.0, rng=None, rng_stream=0, conv=None,
-              colsum_out=None, packed=None, mask_src=None, mask_scale=1.0, batch=None, res_cols=0, bias_strides=None, conv_sub=None):
+              colsum_out=None, packed=None, mask_src=None, mask_scale=1.0, batch=None, res_cols=0, bias_strides=None, conv_sub=None,
+              conv_dil=1):
     """The checked lib.GemmDesc of one product and the tensors it reads or writes (which must outlive its launch).
     packed: the B operand as fragment-ordered bf16 planes (PackedWeights / cape_pack_weights); looked up automatically when B
-    is a parameter (or a view of one) and the product is one the register-stationary kernel takes."""
+    is a parameter (or a view of one) and the product is one the register-stationary kernel takes.
+    conv: the 11-tuple (N, H, W, C, KH, KW, stride, pad, OH, OW, O) of the gather modes; conv_dil: the convolution's dilation
+    (filter tap (kh, kw) reads input pixel (oy * stride - pad + kh * conv_dil, ox * stride - pad + kw * conv_dil))."""
     for t, n in ((A, "A"), (B, "B"), (C, "C"), (bias, "bias"), (scale, "scale"), (residual, "residual")):
         _chk(t, "gemm." + n, contiguous=False)
     if (_AUTO_SPLIT_NN and a_mode == 0 and b_mode == 1 and split_k == 1 and K >= 512 and M > 64 and batch is None and conv is None
@@ -289,6 +292,24 @@ def gemm_desc(A, B, C, M, N, K, a_mode=0, b_mode=0, lda=None, ldb=None, ldc=None
             (d.cPadX, d.cKHp, d.cKWp, d.cTapH0, d.cTapHS, d.cTapW0, d.cTapWS) = conv_sub
             assert a_mode == 3 and b_mode == 2 and _avail(B) >= d.cO * d.cKHp * d.cKWp * d.cC
             assert _avail(A) >= d.cN * d.cOH * d.cOW * d.cO and _avail(C) >= d.cN * d.cH * d.cW * d.cC
+            assert conv_dil == 1, "gemm: a tap sub-lattice takes no dilation"
+        else:
+            # the output extent the gathers assume, and the tensors they index with it (every gather address is bounded by these)
+            assert conv_dil >= 1, "gemm: conv dilation must be >= 1"
+            assert d.cOH == (d.cH + 2 * d.cPad - conv_dil * (d.cKH - 1) - 1) // d.cStride + 1, "gemm: conv OH does not match the geometry"
+            assert d.cOW == (d.cW + 2 * d.cPad - conv_dil * (d.cKW - 1) - 1) // d.cStride + 1, "gemm: conv OW does not match the geometry"
+            n_in, n_out, n_w = d.cN * d.cH * d.cW * d.cC, d.cN * d.cOH * d.cOW * d.cO, d.cO * d.cKH * d.cKW * d.cC
+            if a_mode == 2:
+                assert _avail(A) >= n_in, "gemm: conv input too small"
+            if a_mode == 3:
+                assert _avail(A) >= n_out, "gemm: conv output gradient too small"
+            if b_mode == 2:
+                assert _avail(B) >= n_w, "gemm: conv weight too small"
+            if b_mode == 3:
+                assert _avail(B) >= n_in, "gemm: conv input too small"
+        d.cDil = int(conv_dil)
+    else:
+        assert conv_dil == 1 and conv_sub is None, "gemm: conv_dil / conv_sub need the conv geometry"
     d.scale = scale.data_ptr() if scale is not None else None
     d.bias = bias.data_ptr() if bias is not None else None
     d.residual = residual.data_ptr() if residual is not None else None

@@ -23,13 +23,13 @@ class Conv2dCL(nn.Module):
     """Parameter holder for a bias-free/biased conv whose weight (O, C, KH, KW) is stored channels_last
     (physical (O, KH, KW, C)): the layout the implicit-GEMM kernels stream with 16-byte loads."""
 
-    def __init__(self, cin, cout, k, stride=1, padding=0, bias=False):
+    def __init__(self, cin, cout, k, stride=1, padding=0, bias=False, dilation=1):
         super().__init__()
         w = torch.empty(cout, cin, k, k)
         nn.init.kaiming_normal_(w, mode="fan_out", nonlinearity="relu")
         self.weight = nn.Parameter(w.contiguous(memory_format=torch.channels_last))
         self.bias = nn.Parameter(torch.zeros(cout)) if bias else None
-        self.stride, self.padding, self.kernel_size = stride, padding, k
+        self.stride, self.padding, self.kernel_size, self.dilation = stride, padding, k, dilation
 
     def _load_from_state_dict(self, state_dict, prefix, *a, **kw):
         super()._load_from_state_dict(state_dict, prefix, *a, **kw)
@@ -67,16 +67,18 @@ class FrozenBatchNorm2d(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, dilation=1):
         super().__init__()
         self.conv1 = Conv2dCL(inplanes, planes, 1)
         self.bn1 = FrozenBatchNorm2d(planes)
-        self.conv2 = Conv2dCL(planes, planes, 3, stride=stride, padding=1)      # v1.5: stride on the 3x3
+        # v1.5: stride on the 3x3; torchvision conv3x3(..., dilation): padding = dilation
+        self.conv2 = Conv2dCL(planes, planes, 3, stride=stride, padding=dilation, dilation=dilation)
         self.bn2 = FrozenBatchNorm2d(planes)
         self.conv3 = Conv2dCL(planes, planes * 4, 1)
         self.bn3 = FrozenBatchNorm2d(planes * 4)
         self.downsample = downsample
         self.stride = stride
+        self.dilation = dilation
 
     def forward(self, x):
         bnd = self.downsample[1].folded() if self.downsample is not None else None
@@ -84,13 +86,15 @@ class Bottleneck(nn.Module):
         # one autograd node per block (HF.BottleneckFn): relu(bn3(conv3(...)) + shortcut) in one epilogue, and in the backward
         # conv1's data gradient accumulates into the shortcut's gradient
         return HF.bottleneck(x, self.conv1.weight, self.conv2.weight, self.conv3.weight, wd, self.bn1.folded(), self.bn2.folded(),
-                             self.bn3.folded(), bnd, self.stride)
+                             self.bn3.folded(), bnd, self.stride, self.dilation)
 
 
 class ResNet50Body(nn.Module):
-    """conv1/bn1/maxpool/layer1..4 with the child names IntermediateLayerGetter exposes."""
+    """conv1/bn1/maxpool/layer1..4 with the child names IntermediateLayerGetter exposes.  `dilation`: the DC5 trunk of the
+    reference's `--dilation` (`backbone.py:76-78`, torchvision `replace_stride_with_dilation=[False, False, True]`): layer4 keeps
+    C4's resolution and dilates its 3x3 convolutions instead; same modules, parameter shapes and state_dict keys."""
 
-    def __init__(self, input_channels=3):
+    def __init__(self, input_channels=3, dilation=False):
         super().__init__()
         self.input_channels = input_channels
         self.conv1 = Conv2dCL(input_channels, 64, 7, stride=2, padding=3)
@@ -101,19 +105,26 @@ class ResNet50Body(nn.Module):
             self.conv1.weight.copy_(w)
         self.bn1 = FrozenBatchNorm2d(64)
         self.inplanes = 64
+        self.dilation = 1
         self.layer1 = self._make(64, 3, 1)
         self.layer2 = self._make(128, 4, 2)
         self.layer3 = self._make(256, 6, 2)
-        self.layer4 = self._make(512, 3, 2)
+        self.layer4 = self._make(512, 3, 2, dilate=bool(dilation))
         self._stem_cache = None
 
-    def _make(self, planes, blocks, stride):
+    def _make(self, planes, blocks, stride, dilate=False):
+        # torchvision ResNet._make_layer: a dilated layer trades its stride for dilation, and its FIRST block still runs at the
+        # dilation of the layer before it (`previous_dilation`): in layer4 that block is stride 1, dilation 1
+        previous_dilation = self.dilation
+        if dilate:
+            self.dilation *= stride
+            stride = 1
         ds = None
         if stride != 1 or self.inplanes != planes * 4:
             ds = nn.Sequential(Conv2dCL(self.inplanes, planes * 4, 1, stride=stride), FrozenBatchNorm2d(planes * 4))
-        layers = [Bottleneck(self.inplanes, planes, stride, ds)]
+        layers = [Bottleneck(self.inplanes, planes, stride, ds, previous_dilation)]
         self.inplanes = planes * 4
-        layers += [Bottleneck(self.inplanes, planes) for _ in range(1, blocks)]
+        layers += [Bottleneck(self.inplanes, planes, dilation=self.dilation) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
     def _stem_weight(self):
@@ -185,9 +196,9 @@ class Backbone(BackboneBase):
     def __init__(self, name: str, train_backbone: bool, return_interm_layers: bool, dilation: bool, input_channels=1):
         if name != "resnet50":
             raise ValueError(f"cape_amd implements the reference's default backbone resnet50, got {name}")
-        if dilation:
-            raise ValueError("dilation is not supported by the MI355X backbone")
-        super().__init__(ResNet50Body(input_channels), train_backbone, return_interm_layers)
+        super().__init__(ResNet50Body(input_channels, dilation), train_backbone, return_interm_layers)
+        if dilation:                                        # reference backbone.py:82-83: C5 stays at C4's stride
+            self.strides[-1] = self.strides[-1] // 2
 
 
 class Joiner(nn.Sequential):

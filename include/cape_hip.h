@@ -109,6 +109,16 @@ typedef struct {
      (cTapH0 + kh' * cTapHS, cTapW0 + kw' * cTapWS) of a (cKHp x cKWp) filter.  cKHp == 0: the filter is cKH x cKW as given
      and cPadX = cPad (every earlier caller).  The whole gradient does 2.25 / 9 of the multiplications of the one-launch form. */
   int cPadX, cKHp, cKWp, cTapH0, cTapHS, cTapW0, cTapWS;
+  /* Conv dilation of the gather modes (a_mode 2 / 3, b_mode 3), one value for rows and columns: filter tap (kh, kw) addresses
+     input pixel (oy * cStride - cPad + kh * cDil, ox * cStride - cPad + kw * cDil), so
+     cOH = (cH + 2 * cPad - cDil * (cKH - 1) - 1) / cStride + 1.  Serves torchvision's conv3x3(..., dilation) as
+     resnet50(replace_stride_with_dilation=[False, False, True]) builds it for the reference's `--dilation` trunk
+     (models/backbone.py:76-78: layer4's 3x3 convolutions with dilation 2, padding 2).  Appended under ABI 11 (it fills the
+     struct's tail padding: the size is unchanged); 0 means 1, i.e. a zero-initialised descriptor of an earlier caller behaves as
+     before.  cDil < 0, and cDil > 1 together with the tap sub-lattice fields (cKHp > 0), are rejected on the host -- for EVERY
+     product, dense ones included.  Every caller must therefore zero-initialise the whole struct (memset / `= {0}`) before
+     filling it: a caller that sets the fields of an older header one by one leaves what used to be padding undefined here. */
+  int cDil;
 } cape_gemm_desc;
 
 int cape_gemm_f32(const cape_gemm_desc* d, cape_stream_t stream);
