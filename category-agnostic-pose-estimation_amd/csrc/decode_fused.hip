@@ -17,7 +17,11 @@
 // over the 64 lanes by a transpose-reduce on the VALU (v_permlane32_swap, v_permlane16_swap, DPP row mirror, 8-lane DPP sum).
 // LayerNorms are computed by every wave redundantly from the pre-norm vector in LDS (two wave reductions, no barrier).
 // Single-query attention: wave = head (keys across lanes for q.k, channels across lanes for p.V); the deformable
-// sampling: records by wave 0, gathers by all 8 waves (2 samples each), partial sums through LDS.
+// sampling: records by wave 0, gathers by all 8 waves (2 sample slots each), partial sums through LDS.
+// Samples per head LP = levels x points is a compile-time parameter (4, 12, 16 = 1, 3, 4 levels x 4 points): it sets the row
+// count 8 * LP * 3 of the offsets|weights block (96 / 288 / 384: how many ring pieces stage E consumes and what the stage before
+// it requests), the addressing inside that row, and which of the 16 sample slots per head are live -- the softmax runs over
+// the live ones; a dead slot's record has weight 0 and a clamped row id.
 // Measured: 0.54 ms per step for 2 ... 32 images, 0.63 ms for 128 (GEMV chain alone 0.43 ms = 69 % of the stream rate).
 // LAB_NO_ATTN / LAB_NO_MSDA (compile-time) cut the attention / sampling stages out for timing the chain alone.
 // All arithmetic is plain fp32 FMA.
@@ -264,7 +268,12 @@ constexpr int O_XIN = 0, O_T = 256, O_T2 = 512, O_T3 = 768, O_PRE = 1024, O_Q = 
               O_QPOS = 2304, O_OFFW = 2560 /*384*/, O_G = 2944, O_H = 3200 /*1024*/, O_PART = 4224 /*8 x 256*/, O_RECW = 6272 /*128 x 4*/,
               O_RECI = 6784 /*128 x 2 uint*/, O_SMALL = 7040 /*32*/, O_SC = 7072;
 
+template <int LP>
 __global__ void __launch_bounds__(64 * NW) decode_step_kernel(const DecStepP p) {
+  static_assert(LP >= 1 && LP <= 16, "16 sample slots per head");
+  constexpr int NOFF = NH * LP * 3;                              // rows of the offsets|weights block (<= 384: O_OFFW)
+  constexpr int NQ_E0 = NOFF >= 256 ? NQ : (NOFF + RP - 1) / RP; // ring pieces of its rows 0..255
+  constexpr int NQ_E1 = NOFF > 256 ? (NOFF - 256 + RP - 1) / RP : 0;   // and of its rows 256..
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int n = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   int i8 = ((lane >> 5) & 1) | (((lane >> 4) & 1) << 1) | (((lane >> 3) & 1) << 2);
@@ -350,20 +359,23 @@ __global__ void __launch_bounds__(64 * NW) decode_step_kernel(const DecStepP p) 
 #endif
     __syncthreads();
     x = *reinterpret_cast<const float4*>(sm + O_ATT + 4 * ln);
-    gemv256(Q, x, LW(b_so), 0, 256, NQ, blk(LW(w_off), C, 0, 383, 0), i8, [=](int j, float r) { sm[O_PRE + j] = r + sm[O_T + j]; });
+    gemv256(Q, x, LW(b_so), 0, 256, NQ, blk(LW(w_off), C, 0, NOFF - 1, 0, NQ_E0), i8, [=](int j, float r) { sm[O_PRE + j] = r + sm[O_T + j]; });
     __syncthreads();
     x = ln256(sm + O_PRE, LW(gs), LW(bes));
     if (wave == 0) *reinterpret_cast<float4*>(sm + O_T2 + 4 * ln) = x;
     // ================= E: sampling offsets | attention logits of (tt + query_pos) =================
     {
       const float4 xq = make_float4(x.x + qp.x, x.y + qp.y, x.z + qp.z, x.w + qp.w);
-      gemv256(Q, xq, LW(b_off), 0, 384, NQ, blk(LW(w_off), C, 256, 383, 0, NQ / 2), i8, [=](int j, float r) { sm[O_OFFW + j] = r; });
-      gemv256(Q, xq, LW(b_off), 256, 384, NQ / 2, blk(LW(w_mo), C, 0, 255, 0), i8, [=](int j, float r) { sm[O_OFFW + j] = r; });
+      if constexpr (NQ_E1 > 0) {
+        gemv256(Q, xq, LW(b_off), 0, NOFF, NQ, blk(LW(w_off), C, 256, NOFF - 1, 0, NQ_E1), i8, [=](int j, float r) { sm[O_OFFW + j] = r; });
+        gemv256(Q, xq, LW(b_off), 256, NOFF, NQ_E1, blk(LW(w_mo), C, 0, 255, 0), i8, [=](int j, float r) { sm[O_OFFW + j] = r; });
+      } else {
+        gemv256(Q, xq, LW(b_off), 0, NOFF, NQ_E0, blk(LW(w_mo), C, 0, 255, 0), i8, [=](int j, float r) { sm[O_OFFW + j] = r; });
+      }
     }
     __syncthreads();
     // ================= F: deformable sampling of the cached value projection =================
     {
-      const int LP = p.L * p.NP;
       float4* rec_w = reinterpret_cast<float4*>(sm + O_RECW);
       uint2* rec_i = reinterpret_cast<uint2*>(sm + O_RECI);
 #ifndef LAB_NO_MSDA
@@ -418,7 +430,11 @@ __global__ void __launch_bounds__(64 * NW) decode_step_kernel(const DecStepP p) 
         const int h = ln >> 3, i = ln & 7;
         const float* vb = LW(value) + (long long)n * p.S * C + h * HD + i * 4;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        constexpr int SPW = 16 / NW;                              // L * n_points == 16 (host-checked): samples per wave
+        // sample slots per wave.  Slots >= LP (= L * n_points, host-checked) are dead: the record builder above always writes all 16
+        // records of a head, a dead one with weight 0 and the clamped id S - 1, so a dead slot re-reads one initialised, cache-resident
+        // row and adds 0.  (Skipping them with a wave-uniform branch put control flow in the middle of the live weight ring: the
+        // LP = 4 / 12 instantiations then spilled 115 / 112 VGPRs instead of 52 / 46.)
+        constexpr int SPW = 16 / NW;
         float4 g4[SPW][4];
 #pragma unroll
         for (int q2 = 0; q2 < SPW; ++q2) {
@@ -533,6 +549,19 @@ __global__ void __launch_bounds__(64 * NW) decode_step_kernel(const DecStepP p) 
 }
 
 #undef LW
+template <int LP>
+int launch_step(const DecStepP& p, int N, size_t lds, cape_stream_t stream) {
+  static bool attr_set = false;                                  // per instantiation
+  if (!attr_set) {
+    const size_t max_lds = (size_t)(O_SC + NW * ((MAXKEYS + 4) & ~3)) * sizeof(float);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_step_kernel<LP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
+    if (e != hipSuccess) return cape_set_error("cape_decode_step: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(decode_step_kernel<LP>, dim3(N), dim3(64 * NW), lds, as_stream(stream), p);
+  CAPE_LAUNCH_CHECK("cape_decode_step");
+  return 0;
+}
 inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 }  // namespace
@@ -543,7 +572,9 @@ extern "C" int cape_decode_step(const cape_decode_step_desc* d, cape_stream_t st
   CAPE_REQUIRE(d->n_layers >= 1 && d->n_layers <= CAPE_DECODE_MAX_LAYERS, "cape_decode_step: %d layers, at most %d", d->n_layers, CAPE_DECODE_MAX_LAYERS);
   CAPE_REQUIRE(d->T >= 1 && d->T <= MAXKEYS && d->step >= 0 && d->step < d->T, "cape_decode_step: step %d outside the cache of %d rows (max %d)", d->step, d->T, MAXKEYS);
   CAPE_REQUIRE(d->P >= 0 && d->P <= MAXKEYS, "cape_decode_step: P=%d support keys", d->P);
-  CAPE_REQUIRE(d->L >= 1 && d->L <= 4 && d->n_points >= 1 && d->L * d->n_points == 16, "cape_decode_step: L=%d levels x %d points must be 16", d->L, d->n_points);
+  const int LP = d->L * d->n_points;
+  CAPE_REQUIRE(d->L >= 1 && d->L <= 4 && d->n_points >= 1 && (LP == 4 || LP == 12 || LP == 16),
+               "cape_decode_step: L=%d levels x %d points must be 4, 12 or 16 samples per head", d->L, d->n_points);
   CAPE_REQUIRE(d->S >= 1 && d->S < 65535, "cape_decode_step: S=%d memory tokens (ids are 16 bit)", d->S);
   CAPE_REQUIRE(d->ffn_dim == FFN, "cape_decode_step: ffn_dim=%d, the kernel is built for %d", d->ffn_dim, FFN);
   CAPE_REQUIRE(d->ncls >= 1 && d->ncls <= NW, "cape_decode_step: ncls=%d (one wave per class, at most %d)", d->ncls, NW);
@@ -588,14 +619,5 @@ extern "C" int cape_decode_step(const cape_decode_step_desc* d, cape_stream_t st
   }
   const int scw = ((d->T > d->P ? d->T : d->P) + 1 + 3) & ~3;
   const size_t lds = (size_t)(O_SC + NW * scw) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    const size_t max_lds = (size_t)(O_SC + NW * ((MAXKEYS + 4) & ~3)) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
-    if (e != hipSuccess) return cape_set_error("cape_decode_step: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(decode_step_kernel, dim3(d->N), dim3(64 * NW), lds, as_stream(stream), p);
-  CAPE_LAUNCH_CHECK("cape_decode_step");
-  return 0;
+  return LP == 16 ? launch_step<16>(p, d->N, lds, stream) : LP == 12 ? launch_step<12>(p, d->N, lds, stream) : launch_step<4>(p, d->N, lds, stream);
 }

@@ -1354,10 +1354,10 @@ class DecodeStepPlan:
         for t_, shp in ((Wp, (256, 256)), (bp, (256,)), (gp, (256,)), (bpn, (256,))):
             _chk(t_, "decode_step.pos_trans"); assert tuple(t_.shape) == shp
         d.pos_w, d.pos_b, d.pos_gamma, d.pos_beta = Wp.data_ptr(), bp.data_ptr(), gp.data_ptr(), bpn.data_ptr()
-        P = None
+        P, n_off = None, 8 * geo.L * n_points * 3               # rows of the offsets|weights projection: 96 / 288 / 384 at 1 / 3 / 4 levels
         shapes = {"w_qkv": (768, 256), "b_qkv": (768,), "w_qin": (256, 256), "k_cache": (N, T, 256), "v_cache": (N, T, 256),
                   "w_o": (256, 256), "b_o": (256,), "ln2_g": (256,), "ln2_b": (256,), "w_sq": (256, 256), "b_sq": (256,),
-                  "w_so": (256, 256), "b_so": (256,), "lns_g": (256,), "lns_b": (256,), "w_off": (384, 256), "b_off": (384,),
+                  "w_so": (256, 256), "b_so": (256,), "lns_g": (256,), "lns_b": (256,), "w_off": (n_off, 256), "b_off": (n_off,),
                   "value": (N, geo.S, 256), "w_mo": (256, 256), "b_mo": (256,), "ln1_g": (256,), "ln1_b": (256,),
                   "w1": (ffn_dim, 256), "b1": (ffn_dim,), "w2": (256, ffn_dim), "b2": (256,), "ln3_g": (256,), "ln3_b": (256,),
                   "m1w": (256, 256), "m1b": (256,), "m2w": (256, 256), "m2b": (256,), "m3w": (2, 256), "m3b": (2,)}

@@ -6,7 +6,7 @@ A decode step exists in three tiers; `decode_tier` picks one per call and the ot
   * "stage": one launch per stage of a layer (csrc/decode_step.hip: `decode_linear` with the LayerNorms applied on load,
     `decode_tail`) over folded weights (`DecodeWeights`) + `decode_advance`.  <= 64 images where "whole" does not apply;
   * "whole": the step as ONE launch, one block per image (csrc/decode_fused.hip through `ops.DecodeStepPlan`) +
-    `decode_advance`.  The default; needs the CAPE layer shape (support attention, 4 levels x 4 points, dim_feedforward 1024).
+    `decode_advance`.  The default; needs the CAPE layer shape (support attention, 1, 3 or 4 levels x 4 points, dim_feedforward 1024).
 
 A step works on a few rows, i.e. is host-bound, so the steps are captured as hipGraphs -- one per step index, because the
 cache row written, the attention length and the output slot are baked into the launch arguments -- over the static buffers
@@ -20,6 +20,7 @@ from ..hip import ops
 from .kv_cache import KVCache, VCache
 
 MIN_LEN = 6            # <eos> is accepted from this step on
+WHOLE_STEP_SAMPLES = (4, 12, 16)      # levels x points per head the whole-step kernel is instantiated for (1, 3, 4 levels x 4 points)
 
 
 def _fold(w_in, w_a):
@@ -38,7 +39,7 @@ def _fold(w_in, w_a):
 class DecodeWeights:
     """Inference-time weights of the fused decode step, rebuilt when any source parameter changed
     (version counter or storage): per layer the folded q|k|v projection (768 x 256) and the concatenated
-    sampling_offsets|attention_weights projection (384 x 256)."""
+    sampling_offsets|attention_weights projection (8 * levels * points * 3 rows x 256: 96 / 288 / 384 at 1 / 3 / 4 levels)."""
 
     def __init__(self, decoder):
         self.decoder, self.key, self.layers = decoder, None, None
@@ -71,11 +72,12 @@ class DecodeWeights:
         return self.layers
 
 
-def alloc_decode_workspace(N, n_layers, L, dev):
-    """Static per-geometry buffers of the fused step (pre-norm sums p1..p4, projections, per-layer query positions)."""
+def alloc_decode_workspace(N, n_layers, L, dev, samples_per_head=16):
+    """Static per-geometry buffers of the fused step (pre-norm sums p1..p4, projections, per-layer query positions);
+    `offw` is a row of the offsets|weights projection: 8 heads x samples_per_head (levels x points) x 3."""
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     return {"emb": f(N, 256), "q": f(N, 256), "qs": f(N, 256), "p1": f(N, 256), "p2": f(N, 256), "p3": f(N, 256),
-            "p4": [f(N, 256) for _ in range(n_layers)], "offw": f(N, 384), "h": f(N, 1024),
+            "p4": [f(N, 256) for _ in range(n_layers)], "offw": f(N, 8 * samples_per_head * 3), "h": f(N, 1024),
             "qpos": [None] + [f(N, 256) for _ in range(n_layers - 1)], "refin": [None] + [f(N, L, 2) for _ in range(n_layers - 1)],
             "ref": [None] + [f(N, 2) for _ in range(n_layers)]}
 
@@ -160,7 +162,7 @@ def decode_tier(N, P, samples_per_head, ffn_dim, seq_len, S, n_layers, num_class
     """"per_op" | "stage" | "whole" (module docstring) for N images with P support keypoints; samples_per_head = levels x
     points of the decoder's MSDA, S = image tokens.  CAPE_DECODE_FUSED=0 / CAPE_DECODE_MEGA=0 step down a tier for A/B."""
     fused = os.environ.get("CAPE_DECODE_FUSED", "1") == "1"
-    whole = (fused and os.environ.get("CAPE_DECODE_MEGA", "1") == "1" and P > 0 and samples_per_head == 16 and ffn_dim == 1024 and
+    whole = (fused and os.environ.get("CAPE_DECODE_MEGA", "1") == "1" and P > 0 and samples_per_head in WHOLE_STEP_SAMPLES and ffn_dim == 1024 and
              seq_len <= 1024 and P <= 1024 and S < 65535 and n_layers <= 8 and num_classes <= 8)
     return "whole" if whole else "stage" if fused and N <= 64 else "per_op"      # the launch-per-stage kernels take <= 64 rows
 
@@ -190,7 +192,7 @@ class DecodeState:
                         "sup_kpm": torch.empty(N, P, dtype=torch.uint8, device=dev) if (P and has_mask) else None}
                        for kv, vc in zip(self.kv, self.vc)]
         if tier != "per_op":
-            self.ws = alloc_decode_workspace(N, len(dec.layers), geo.L, dev)
+            self.ws = alloc_decode_workspace(N, len(dec.layers), geo.L, dev, geo.L * dec.layers[0].cross_attn.n_points)
             # layer-0 tables (its reference points are the learned anchors, the same for every image): query position
             # embedding per step, the (N, 2) reference rows the tail kernel refines and their level-scaled points
             self.qpos0, self.ref0 = torch.empty(T0, 256, device=dev), torch.empty(max_len, N, 2, device=dev)

@@ -3,8 +3,9 @@ reference (`models/deformable_transformer.py:39-291`); the computation is re-lai
 
   * tokens stay in one flattened (N, S, 256) fp32 buffer; q = src + pos is emitted by the LayerNorm
     kernel that produces src (no separate add pass);
-  * sampling offsets and attention logits come from one (N*S, 384) projection buffer that the MSDA
-    kernel consumes directly (softmax over the 16 samples fused into the gather);
+  * sampling offsets and attention logits come from one (N*S, 8 * levels * points * 3) projection buffer (384 columns at
+    4 levels x 4 points, 288 at 3, 96 at 1) that the MSDA kernel consumes directly (softmax over the levels * points
+    samples fused into the gather);
   * `self.normK(src + self.dropoutK(x))` is one kernel; `relu + dropout` ride in the GEMM epilogue.
 """
 import copy

@@ -47,8 +47,16 @@ class RoomFormerV2(nn.Module):
         if cape_mode:
             raise ValueError("cape_mode=True (RoomFormerV2-internal SupportPoseEncoder) is not on the CAPE path; "
                              "models.build_model always passes cape_mode=False")
-        if not with_poly_refine or use_anchor or inject_cls_embed or num_feature_levels != 4:
-            raise ValueError("CAPE path: with_poly_refine=True, use_anchor=False, inject_cls_embed=False, 4 feature levels")
+        if not with_poly_refine or use_anchor or inject_cls_embed:
+            raise ValueError("CAPE path: with_poly_refine=True, use_anchor=False, inject_cls_embed=False")
+        if num_feature_levels not in (1, 3, 4):
+            # 2: the reference itself builds three input_proj (C3..C5) against a two-row level_embed; 5: the MSDA kernels take <= 4
+            raise ValueError(f"num_feature_levels={num_feature_levels}: 1 (C5 only), 3 (C3..C5) or 4 (C3..C5 + one stride-2 level); "
+                             "2 is inconsistent in the reference (three input_proj, two level_embed rows) and the MSDA kernels "
+                             "take at most 4 levels")
+        if len(backbone.strides) != min(num_feature_levels, 3):
+            raise ValueError(f"{num_feature_levels} feature levels need a backbone with {min(num_feature_levels, 3)} outputs, "
+                             f"got {len(backbone.strides)} (build_backbone: return_interm_layers = num_feature_levels > 1)")
         self.num_queries, self.num_polys = num_queries, num_polys
         self.transformer = transformer
         hidden_dim = transformer.d_model
@@ -66,9 +74,11 @@ class RoomFormerV2(nn.Module):
         num_backbone_outs = len(backbone.strides)
         proj = []
         in_channels = None
+        # (one level: the reference's else-branch, a 1x1 projection of C5 whatever the patch size, roomformer_v2.py:209-214)
+        k_proj = patch_size if num_feature_levels > 1 else 1
         for i in range(num_backbone_outs):
             in_channels = backbone.num_channels[i]
-            proj.append(nn.Sequential(Conv2dCL(in_channels, hidden_dim, patch_size, stride=patch_size, padding=0, bias=True),
+            proj.append(nn.Sequential(Conv2dCL(in_channels, hidden_dim, k_proj, stride=k_proj, padding=0, bias=True),
                                       nn.GroupNorm(32, hidden_dim)))
         for _ in range(num_feature_levels - num_backbone_outs):
             if patch_size == 1:
@@ -138,7 +148,7 @@ class RoomFormerV2(nn.Module):
                 x, last = HF.fanout(x, 2)        # C5 also feeds the extra stride-2 level
             conv = self.input_proj[l][0]
             src = HF.conv_bn_act(x, conv.weight, None, conv.bias, conv.stride, conv.padding, relu=False)
-            if self.patch_size != 1:
+            if conv.stride != 1:
                 mask = level_mask(mask, src)
             srcs.append(src); masks.append(mask)
         for l in range(len(features), self.num_feature_levels):

@@ -85,7 +85,7 @@ def split_groups(model):
 def _colocate(named):
     """Physical order inside an arena is ours to choose (optimizer state and checkpoints go by name).  MSDeformAttn's
     `sampling_offsets` and `attention_weights` always multiply the same rows: their weights are placed back to back
-    (and their biases), so that the pair is ONE (384, 256) operand for a single launch (hip/functional.LinearCat2Fn)."""
+    (and their biases), so that the pair is ONE (8 * levels * points * 3, 256) operand -- 384 rows at 4 levels, 288 at 3, 96 at 1 -- for a single launch (hip/functional.LinearCat2Fn)."""
     out = list(named)
     for i in range(len(out) - 2):
         a, b, c = out[i][0], out[i + 1][0], out[i + 2][0]

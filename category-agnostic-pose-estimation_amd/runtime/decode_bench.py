@@ -27,7 +27,8 @@ def decoder_step_bytes(model):
     return 4 * n
 
 
-def decode_benchmark(device, episodes=1, image_size=512, keypoints=68, shots=5, queries=2, reps=3, seed=3, model=None, tok=None):
+def decode_benchmark(device, episodes=1, image_size=512, keypoints=68, shots=5, queries=2, reps=3, seed=3, model=None, tok=None, extra=()):
+    """`extra`: further CLI flags of the model that is built when none is passed (e.g. ("--num_feature_levels", "1", "--dilation"))."""
     import cape_amd  # noqa: F401
     from cape_amd.datasets import DiscreteTokenizerV2, episodic_collate_fn
     from cape_amd.datasets.synthetic import SyntheticEpisodes
@@ -36,7 +37,7 @@ def decode_benchmark(device, episodes=1, image_size=512, keypoints=68, shots=5, 
     from cape_amd.models.train_cape_episodic import get_args_parser
     if model is None:
         args = argparse.ArgumentParser(parents=[get_args_parser()]).parse_args(
-            ["--use_geometric_encoder", "--use_gcn_preenc", "--image_size", str(image_size)])
+            ["--use_geometric_encoder", "--use_gcn_preenc", "--image_size", str(image_size), *extra])
         torch.manual_seed(0)
         tok = DiscreteTokenizerV2(44, args.seq_len)
         base, _ = build_model(args, tokenizer=tok)

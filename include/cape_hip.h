@@ -204,11 +204,11 @@ int cape_decode_tail(const cape_decode_tail_desc* d, cape_stream_t stream);
  *   per layer l:  q|k|v = x W_qkv^T + b (folded attn_{q,k,v} . in_proj), q += query_pos W_qin^T; k, v -> row `step` of the
  *   layer's cache; single-query self-attention over rows 0..step (8 heads x 32); out_proj + residual, norm2; [support
  *   cross-attention over P cached keys with key-padding mask, out_proj + residual, norm_support]; sampling_offsets |
- *   attention_weights of (t + query_pos); softmax over L*n_points = 16 logits per head + bilinear gather from the cached
+ *   attention_weights of (t + query_pos); softmax over the L*n_points (4, 12 or 16) logits per head + bilinear gather from the cached
  *   value projection (N, S, 256); output_proj + residual, norm1; linear1 + ReLU, linear2 + residual; norm3; coords MLP
  *   (256-256-256-2) + refinement sigmoid(delta + logit(ref)); [last layer: class head, hidden state] / [else: next layer's
  *   query position embedding LN(pos_trans(sine(ref'))) and level-scaled reference points ref' * valid_ratio].
- * All matrices row-major [out][in] fp32, 16-byte aligned.  Model width 256, 8 heads, L * n_points == 16, ffn_dim a multiple
+ * All matrices row-major [out][in] fp32, 16-byte aligned.  Model width 256, 8 heads, L * n_points in {4, 12, 16} (1, 3 or 4 levels x 4 points), ffn_dim a multiple
  * of 256 (<= 1024), S < 65535, cache rows T <= 1024, P <= 1024.  w_sq == NULL: no support attention in that layer.
  * ---------------------------------------------------------------------------------------------- */
 #define CAPE_DECODE_MAX_LAYERS 8
@@ -221,7 +221,7 @@ typedef struct {
   const float *sup_k, *sup_v;            /* (N, P, 256) projected support keys / values */
   const unsigned char* sup_mask;         /* (N, P) nonzero = padded key, or NULL */
   const float *w_so, *b_so, *lns_g, *lns_b;
-  const float *w_off, *b_off;            /* (384, 256) sampling_offsets | attention_weights, (384,) */
+  const float *w_off, *b_off;            /* (8*L*n_points*3, 256) sampling_offsets | attention_weights, and its bias */
   const float* value;                    /* (N, S, 256) cached value projection of the image memory */
   const float *w_mo, *b_mo, *ln1_g, *ln1_b;
   const float *w1, *b1, *w2, *b2;        /* (F, 256), (F,), (256, F), (256,) */
